@@ -1,6 +1,10 @@
 """bench.py — throughput of the siamese-FCOS hot path on MI355X (contract: see the task's bench section / DESIGN.md §5).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype bf16|f32] [--batch 8] [--no-cpu-baseline]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dtype bf16|f32] [--batch 8] [--dump-outputs DIR] [--full]
+  A plain run sets up, tunes, warms up, times the K steps and prints the result line.  --full adds what the headline does not
+  need: the per-launch conv timing pass after the timed region (`roofline`, `roofline_correlation`, --layer-table) and the
+  CPU baseline (`cpu_baseline`; --no-conv-timing / --no-cpu-baseline drop either of them again).
+  --dump-outputs DIR: after the timed steps, what the last timed step computed as DIR/<name>.npy (float32 / float64).
   N > 1:  python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
               bench.py --gpus N --steps K --warmup W
           or simply `python bench.py --gpus N`: with no WORLD_SIZE in the environment the process starts N ranks of itself
@@ -444,6 +448,46 @@ def result_line(args, world, batch, elapsed, workload, launch, roofline=None, cp
     return line
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+DUMP_MAX_ELEMENTS = 1 << 20     # a larger array is written as this many elements at fixed, seeded flat indices
+
+
+def dump_outputs(dirname, arrays):
+    """--dump-outputs: every (name, tensor) as DIR/<name>.npy, floating tensors as float32 and integer ones as float64 (exact).
+    An array of more than DUMP_MAX_ELEMENTS elements is written as the elements at a sorted sample of its flat indices, seeded by
+    its name and size: every run and every build of the project samples the same positions."""
+    import zlib
+    import numpy as np
+    out = []
+    for name, t in arrays:
+        t = t.detach()
+        a = (t.float() if t.is_floating_point() else t.double()).cpu().numpy()
+        if a.size > DUMP_MAX_ELEMENTS:
+            rng = np.random.default_rng(zlib.crc32(("%s:%d" % (name, a.size)).encode()))
+            a = a.reshape(-1)[np.unique(rng.integers(0, a.size, DUMP_MAX_ELEMENTS))]
+        out.append((name, a))
+    total = sum(a.nbytes for _, a in out)
+    if total > DUMP_BUDGET_BYTES:
+        raise RuntimeError("--dump-outputs: %d bytes exceed the %d-byte budget" % (total, DUMP_BUDGET_BYTES))
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in out:
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
+def keeping_last(step, last):
+    """step() that also keeps what it returned in last[0]: what --dump-outputs writes after the timed steps"""
+    def run():
+        last[0] = step()
+        return last[0]
+    return run
+
+
+def valid_rows(x, counts):
+    """boxes / scores padded past each image's count: the rows past the count are not results, they are written as zeros"""
+    keep = torch.arange(x.shape[1], device=x.device)[None, :] < counts.to(x.device).long()[:, None]
+    return torch.where(keep.view(keep.shape + (1,) * (x.dim() - 2)), x, torch.zeros_like(x))
+
+
 def measured_peaks(dtype):
     """Yardsticks measured on the box (profiles/r1_peak_probe.json: bare MFMA loop, streaming copy, vendor GEMM) reported
     beside the datasheet peak the `frac` is taken against."""
@@ -741,12 +785,21 @@ def main_train(args, rank, world, backend="nccl"):
             print("graph capture failed, running eagerly: %r" % (e,), file=sys.stderr)
             torch.cuda.synchronize()
 
+    last = [None]
+    if args.dump_outputs:
+        step = keeping_last(step, last)
     elapsed = timed_steps(step, args.steps, args.warmup, world, torch.cuda.synchronize, "cuda")
     # outside the timed region: a one-pass GroupNorm launch whose hand-off timed out has written NaN and set its error word — such a
     # run is not a measurement (raises OsdError -> non-zero exit, no JSON line)
     ops.gn_onepass_check("bench.py, after the timed training steps")
+    if args.dump_outputs and rank == 0:
+        # the last timed step's losses (cls, reg, centerness, num_pos) and the weights its update left (the fp32 master copy)
+        arrays = [("losses", last[0])]
+        if two and torch.is_tensor(eng.box_losses):
+            arrays.append(("box_losses", eng.box_losses))
+        dump_outputs(args.dump_outputs, arrays + [("weights", eng.flat_w)])
     roofline = None
-    if not args.no_conv_timing:
+    if args.full and not args.no_conv_timing:
         timer = TrainTimer()
         timer.install(ops)
         torch.cuda.synchronize()
@@ -864,7 +917,7 @@ def main_train(args, rank, world, backend="nccl"):
         if two:
             workload += (" + second stage (subsample 128 ROIs per image, few-shot ROI box head forward, cross-entropy + "
                          "smooth-L1, backward into both backbones)")
-        cpu = cpu_baseline(args.dtype, train=True, shapes=shapes, shots=S) if (world == 1 and not args.no_cpu_baseline) else None
+        cpu = cpu_baseline(args.dtype, train=True, shapes=shapes, shots=S) if (args.full and world == 1 and not args.no_cpu_baseline) else None
         line = result_line(args, world, B, elapsed, workload, launch, roofline, cpu)
         if args.workload == "config5":
             line["metric"] = "images/sec/GPU fwd+bwd, multi-scale {640,800,1024} short-edge target + 5-shot 127x127 query stack, bs=4"
@@ -912,9 +965,13 @@ def main():
     ap.add_argument("--workload", default="config3", choices=sorted(WORKLOADS),
                     help="train mode: config3 = BASELINE.json configs[2]/[3], the headline (800x1024, 1 shot, bs 8); config5 = "
                          "configs[4]'s per-GPU workload (multi-scale 640/800/1024 short edge, 5-shot query stack, bs 4)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-conv-timing", action="store_true")
-    ap.add_argument("--layer-table", default="", help="train mode: write the per-shape conv table (markdown) here")
+    ap.add_argument("--full", action="store_true",
+                    help="also the measurements beside the headline: the conv timing pass (roofline) and the CPU baseline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, <= 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-conv-timing", action="store_true", help="--full without the conv timing pass")
+    ap.add_argument("--layer-table", default="", help="train mode, --full: write the per-shape conv table (markdown) here")
     ap.add_argument("--no-graph", action="store_true", help="forward mode: eager launches instead of hipGraph replay")
     ap.add_argument("--graph", action="store_true",
                     help="train mode: replay the step from hipGraphs (measured slower than eager 2-stream launches: the "
@@ -933,6 +990,10 @@ def main():
     ap.add_argument("--dry-run-cpu", action="store_true",
                     help="exercise only the multi-process plumbing (gloo, no GPU work): used by tests/test_dist_cpu.py")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.layer_table and not (args.full and not args.no_conv_timing):
+        ap.error("--layer-table is written by the conv timing pass: add --full")
 
     if not args.batch:
         args.batch = WORKLOAD_BATCH[args.workload]
@@ -984,15 +1045,32 @@ def main():
         def step():
             return eng.detect(images, queries, second_stage=two)
 
+    last = [None]
+    if args.dump_outputs:
+        step = keeping_last(step, last)
     elapsed = timed_steps(step, args.steps, args.warmup, world, torch.cuda.synchronize, "cuda")
     ops.gn_onepass_check("bench.py, after the timed forward passes")      # see main_train
+    if args.dump_outputs and rank == 0:
+        # the last timed pass's FCOS head outputs per level (NCHW fp32: logits + centerness, box regression), its proposals and,
+        # with --second-stage, its detections
+        out = last[0]
+        arrays = []
+        for lvl, (cc, rg) in enumerate(out["head"]):
+            arrays += [("head_p%d_cls_ctr" % (lvl + 3), ops.nhwc_to_nchw_f32(cc, 0, 2)), ("head_p%d_reg" % (lvl + 3), ops.nhwc_to_nchw_f32(rg))]
+        pb, ps, pc = out["proposals"]
+        arrays += [("proposals_boxes", valid_rows(pb, pc)), ("proposals_scores", valid_rows(ps, pc)), ("proposals_counts", pc)]
+        if two:
+            det = out["detections"]
+            arrays += [("detections_boxes", valid_rows(det["boxes"], det["counts"])),
+                       ("detections_scores", valid_rows(det["scores"], det["counts"])), ("detections_counts", det["counts"])]
+        dump_outputs(args.dump_outputs, arrays)
 
     # Roofline of the dominant kernel family (conv_igemm): HIP events around every conv launch, on the stream the
     # kernel is launched on, over `steps` further steps of the SAME workload in this process, run eagerly on one
     # stream (kernels inside a replayed hipGraph cannot be bracketed individually, and concurrent branches would
     # inflate each other's durations).
     roofline = None
-    if not args.no_conv_timing:
+    if args.full and not args.no_conv_timing:
         timer = ConvTimer()
         timer.install(ops)
         torch.cuda.synchronize()
@@ -1024,7 +1102,7 @@ def main():
                     % (B, " + second-stage ROI box head on the proposals (7x7 level-routed ROIAlign, concat with the "
                           "query ROI map, 3 conv+GN+LeakyReLU, fc6, fc7, predictor, decode, NMS 0.5)" if two else "",
                        args.dtype))
-        cpu = cpu_baseline(args.dtype) if (world == 1 and not args.no_cpu_baseline) else None
+        cpu = cpu_baseline(args.dtype) if (args.full and world == 1 and not args.no_cpu_baseline) else None
         line = result_line(args, world, B, elapsed, workload,
                            "hipGraph replay, 4 streams" if use_graph else "eager, 4 streams", roofline, cpu)
         print(json.dumps(line), flush=True)

@@ -6,6 +6,8 @@ import socket
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -81,3 +83,34 @@ def test_gradient_average_two_ranks():
     assert "RANK 0 EXCHANGE=True" in out.stdout and "RANK 1 EXCHANGE=True" in out.stdout
     # dist_utils.broadcast_tuner_choices: both ranks end with rank 0's kernel choices (same worker, third part)
     assert "RANK 0 TUNER=True" in out.stdout and "RANK 1 TUNER=True" in out.stdout
+
+
+def test_bench_dump_outputs_writes_fixed_samples_within_the_budget(tmp_path):
+    """--dump-outputs: float32 for floating tensors, float64 for integer ones, rows past an image's count zeroed; an array larger
+    than DUMP_MAX_ELEMENTS becomes a sample at the same positions in every run; more than 64 MB in all is refused."""
+    import numpy as np
+    import torch
+    import bench
+    boxes, counts = torch.arange(24, dtype=torch.bfloat16).view(2, 3, 4) + 1, torch.tensor([2, 0], dtype=torch.int32)
+    big = torch.randn(3 * bench.DUMP_MAX_ELEMENTS)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), [("boxes", bench.valid_rows(boxes, counts)), ("counts", counts), ("big", big)])
+    b = np.load(str(tmp_path / "a" / "boxes.npy"))
+    assert b.dtype == np.float32 and b.shape == (2, 3, 4)
+    assert (b[0, :2] == boxes[0, :2].float().numpy()).all() and not b[0, 2:].any() and not b[1].any()
+    c = np.load(str(tmp_path / "a" / "counts.npy"))
+    assert c.dtype == np.float64 and c.tolist() == [2.0, 0.0]
+    s1, s2 = np.load(str(tmp_path / "a" / "big.npy")), np.load(str(tmp_path / "b" / "big.npy"))
+    assert s1.dtype == np.float32 and 0 < s1.size <= bench.DUMP_MAX_ELEMENTS and np.array_equal(s1, s2)
+    assert np.isin(s1, big.numpy()).all()
+    with pytest.raises(RuntimeError):
+        bench.dump_outputs(str(tmp_path / "c"), [("big%d" % i, big) for i in range(24)])
+    assert not (tmp_path / "c").exists()
+
+
+def test_bench_refuses_zero_steps_and_a_layer_table_without_full():
+    for extra in (["--steps", "0"], ["--layer-table", "t.md"]):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--dry-run-cpu"] + extra, capture_output=True,
+                             text=True, timeout=120, cwd=ROOT)
+        assert out.returncode == 2 and "error" in out.stderr, extra
+        assert not [l for l in out.stdout.splitlines() if l.startswith("{")]

@@ -1171,6 +1171,29 @@ def test_bench_self_launches_two_ranks_sharing_the_gpu():
         assert out.returncode == 2 and "GPU(s) visible" in out.stderr
 
 
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_one(tmp_path):
+    """`bench.py --steps 3 --warmup 1 --dump-outputs DIR`: the headline line only (no conv timing pass, no CPU baseline: those
+    are --full's), exactly the steps asked for, and the last timed step's losses and a sample of the updated weights."""
+    import json
+    import os
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                          "--dump-outputs", str(tmp_path)], capture_output=True, text=True, timeout=600, cwd=root)
+    assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-3000:]
+    lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1
+    r = json.loads(lines[0])
+    assert r["steps"] == 3 and r["step_ms"]["n"] == 3 and r["ms_per_step"] > 0 and r["dtype"] == "bf16"
+    assert abs(r["value"] - 8 * 1e3 / r["ms_per_step"]) / r["value"] < 0.01
+    assert r["roofline"] is None and "cpu_baseline" not in r and "roofline_correlation" not in r
+    assert sorted(os.listdir(str(tmp_path))) == ["losses.npy", "weights.npy"]
+    losses, w = np.load(str(tmp_path / "losses.npy")), np.load(str(tmp_path / "weights.npy"))
+    assert losses.dtype == np.float32 and losses.shape == (4,) and np.isfinite(losses).all() and losses[3] > 0
+    assert w.dtype == np.float32 and 0 < w.size <= 1 << 20 and np.isfinite(w).all()
+
+
 def test_config5_multiscale_five_shot_training_steps():
     """BASELINE.json configs[4] at full size: bs=4, S=5 queries per image (20 x 127x127), the target's short edge cycling
     through {640, 800, 1024} (640x832, 800x1024, 1024x1312) from step to step on ONE engine (buffers keyed by shape).

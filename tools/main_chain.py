@@ -2,7 +2,7 @@
 their backward).  From a rocprofv3 kernel trace of bench.py: per timed step, how long the main queue was busy, how long it sat
 between two of its kernels (waiting for another stream or for the host), and per kernel family the time inside the multi-stream
 step against the same launches in the single-stream roofline pass that follows the timed region.
-usage: rocprofv3 --kernel-trace --output-format csv -d DIR -o run -- python3 bench.py --steps 12 --warmup 4 --no-cpu-baseline
+usage: rocprofv3 --kernel-trace --output-format csv -d DIR -o run -- python3 bench.py --full --steps 12 --warmup 4 --no-cpu-baseline
        python tools/main_chain.py DIR/.../run_kernel_trace.csv [timed steps] [roofline-pass steps]"""
 import collections
 import csv

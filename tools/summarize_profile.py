@@ -1,4 +1,4 @@
-"""Summarise a `rocprofv3 --kernel-trace --stats --output-format csv` run of bench.py into a small markdown file.
+"""Summarise a `rocprofv3 --kernel-trace --stats --output-format csv` run of `bench.py --full` into a small markdown file.
 
   python tools/summarize_profile.py gpurun_out/prof_<tag> profiles/<name>.md [steps]
 
