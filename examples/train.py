@@ -2,6 +2,7 @@
 RyanXLi/OneshotDet drive it (both stages, SGD with the reference's parameter groups, periodic checkpoints, resume):
 
     python examples/train.py [--iters 20] [--batch 2] [--dtype bf16|f32] [--first-stage-only] [--out /tmp/osd_run]
+                             [--shared-backbone]        # one backbone for target and query (SIAMESE_BACKBONE False)
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 examples/train.py ...      # one rank per GPU
 
   * data: `dataset.FewShotCocoDataset` (= the reference's COCODataset: one item per (category, image), seeded epoch order,
@@ -52,18 +53,20 @@ def main():
     ap.add_argument("--out", default="/tmp/osd_example_run")
     ap.add_argument("--resume", action="store_true")
     ap.add_argument("--checkpoint-period", type=int, default=10)
+    ap.add_argument("--shared-backbone", action="store_true", help="one backbone for target and query (SIAMESE_BACKBONE False)")
     args = ap.parse_args()
+    siamese = not args.shared_backbone
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
     dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float32
-    shapes = spec.hot_path_shapes() if args.first_stage_only else spec.full_model_shapes()
+    shapes = spec.hot_path_shapes(siamese) if args.first_stage_only else spec.full_model_shapes(siamese)
 
     def make_engine(sd):
-        return train.TrainEngine(sd, dtype=dtype, lr=0.0005, second_stage=not args.first_stage_only)
+        return train.TrainEngine(sd, dtype=dtype, lr=0.0005, second_stage=not args.first_stage_only, siamese_backbone=siamese)
     start = 0
     last = os.path.join(args.out, "last_checkpoint")
     if args.resume and os.path.exists(last):
-        eng, start = checkpoint.resume_training(open(last).read().strip(), make_engine)
+        eng, start = checkpoint.resume_training(open(last).read().strip(), make_engine, siamese_backbone=siamese)
         print("resumed at iteration", start)
     else:
         eng = make_engine(synth.make_state_dict(shapes))      # or checkpoint.load_checkpoint / load_c2_resnet, see detect.py

@@ -378,6 +378,13 @@ int osd_conv2d_wgrad_multi(const osd_conv_desc* d, int n_seg, const void* const*
  * taken from descs[0]; descs is a HOST array of n_seg descriptors. */
 int osd_conv2d_wgrad_mixed(int n_seg, const osd_conv_desc* descs, const void* const* xs, const void* const* dys,
                            const float* const* scales, float* const* dws, float* const* dbs, void* stream);
+/* Cross-launch rule for every atomic-mode weight-gradient launch above: a segment whose dW no other segment OF THE SAME
+ * LAUNCH names, and that gets one pixel split, may add into dW with a plain load + store (owner mode) instead of atomics.
+ * A launch cannot see other launches, so while owner mode is possible NO OTHER LAUNCH may add into the same dW
+ * concurrently (another stream, or a graph branch that is not ordered with this one): two writers of one dW either go into
+ * ONE launch (segments that repeat the dW pointer: atomic adds or the ordered reduction) or into launches ordered one after
+ * the other (the same stream).  Launches that follow each other on one stream accumulate correctly in either mode.
+ * (The shared-backbone training step is such a caller: its target and query branches add into one dW per conv.) */
 /* packed fp32 dW [cout][r][s][cin] -> OIHW fp32 gradient, multiplied by the folded FrozenBN scale (nullable);
  * accumulate != 0 adds to grad_oihw (weights shared over FPN levels) */
 int osd_unpack_wgrad(const float* dw_packed, const float* scale, float* grad_oihw, int cout, int cin, int r, int s,

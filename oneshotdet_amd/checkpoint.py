@@ -7,6 +7,9 @@ expected key the loaded key that is its LONGEST suffix), so a reference `model_X
 The Caffe2 / Detectron `.pkl` route (utils/c2_model_loading.py:12-175; `MODEL.WEIGHT: catalog://ImageNetPretrained/MSRA/R-50`)
 is `load_c2_resnet`: blob names are translated to the torchvision-style names the reference maps them to, and the same
 suffix alignment then fills BOTH backbones (every `*.body.layer1.0.conv1.weight` ends with `layer1.0.conv1.weight`).
+siamese_backbone (FEW_SHOT.SIAMESE_BACKBONE): True = the two-backbone model (a shared-backbone file fills `supp_backbone.*` from
+`backbone.*` by that suffix match, as the reference does); False = the shared-backbone model, whose key set has no
+`supp_backbone.*` (a two-backbone file's query backbone is ignored, as the reference ignores keys its model does not have).
 """
 import os
 import pickle
@@ -48,18 +51,33 @@ def align_state_dict(expected_shapes, loaded):
     return out, missing
 
 
-def load_checkpoint(path, second_stage=None, defaults=None):
-    """Read a reference `.pth` (or a bare state_dict file) -> (state_dict under the reference's key names, extras).
-    second_stage: True = require roi_heads.box.*, False = first stage only, None = take it when present.
-    defaults: values for keys the file lacks (utils/checkpoint.py:107-115 keeps the model's own initialisation for
-    FEW_SHOT.UNLOAD_KEYWORD modules); without it a missing key is an error."""
+def _read(path):
     data = torch.load(path, map_location="cpu", weights_only=False)
     if not isinstance(data, dict):
         raise ValueError("%s: not a checkpoint dictionary" % path)
     if "model" not in data:                                            # checkpoint.py:164-165
         data = {"model": data}
+    return data
+
+
+def has_query_backbone(path_or_sd):
+    """True iff a checkpoint file (or a state_dict) holds a query backbone of its own (`supp_backbone.*`): it was written by a
+    two-backbone model (FEW_SHOT.SIAMESE_BACKBONE True).  Picks the mode to build a model in from a file."""
+    sd = path_or_sd
+    if isinstance(path_or_sd, (str, bytes, os.PathLike)):
+        sd = _read(path_or_sd)["model"]
+    return any(k.startswith("supp_backbone.") for k in strip_prefix_if_present(sd))
+
+
+def load_checkpoint(path, second_stage=None, defaults=None, siamese_backbone=True):
+    """Read a reference `.pth` (or a bare state_dict file) -> (state_dict under the reference's key names, extras).
+    second_stage: True = require roi_heads.box.*, False = first stage only, None = take it when present.
+    defaults: values for keys the file lacks (utils/checkpoint.py:107-115 keeps the model's own initialisation for
+    FEW_SHOT.UNLOAD_KEYWORD modules); without it a missing key is an error.
+    siamese_backbone=False: read the shared-backbone model's keys only (any `supp_backbone.*` in the file is ignored)."""
+    data = _read(path)
     loaded = data.pop("model")
-    shapes = spec.hot_path_shapes()
+    shapes = spec.hot_path_shapes(siamese_backbone)
     box = spec.box_head_shapes()
     probe = strip_prefix_if_present(loaded)
     has_box = any(k.endswith("box.fc6.weight") for k in probe)
@@ -90,19 +108,36 @@ def save_checkpoint(path, state_dict, tag_last=True, **extras):
 
 def save_training_checkpoint(path, engine, iteration, tag_last=True):
     """utils/checkpoint.py:33-50 as the trainer calls it (engine/trainer.py:111-119): model + optimizer + iteration.
-    `optimizer` holds TrainEngine.optimizer_state_dict() (momentum buffers under reference names, steps taken, lr)."""
+    `optimizer` holds TrainEngine.optimizer_state_dict() (momentum buffers under reference names, steps taken, lr);
+    `siamese_backbone` the engine's mode (a shared engine writes no `supp_backbone.*`)."""
     return save_checkpoint(path, engine.state_dict(), tag_last=tag_last, optimizer=engine.optimizer_state_dict(),
-                           iteration=int(iteration))
+                           iteration=int(iteration), siamese_backbone=bool(getattr(engine, "siamese_backbone", True)))
 
 
-def resume_training(path, make_engine):
+def resume_training(path, make_engine, siamese_backbone=None):
     """Load a checkpoint written by save_training_checkpoint: make_engine(state_dict) -> TrainEngine; its momentum and
-    step count are restored.  Returns (engine, iteration)."""
-    sd, extras = load_checkpoint(path)
+    step count are restored.  Returns (engine, iteration).  The file's mode (recorded by save_training_checkpoint; for
+    older files: whether it holds `supp_backbone.*`) must be the engine's: a resumed run never ties or unties weights
+    behind the caller's back.  siamese_backbone: the mode the caller expects (None: whatever the file holds)."""
+    data = _read(path)
+    mode = data.get("siamese_backbone")
+    mode = has_query_backbone(data["model"]) if mode is None else bool(mode)
+    if siamese_backbone is not None and bool(siamese_backbone) != mode:
+        raise ValueError("%s holds a %s model; resuming it as a %s model would %s the query backbone's weights: load it with "
+                         "load_checkpoint(..., siamese_backbone=%r) into a fresh run instead"
+                         % (path, _MODE[mode], _MODE[bool(siamese_backbone)], "untie" if siamese_backbone else "tie",
+                            bool(siamese_backbone)))
+    sd, extras = load_checkpoint(path, siamese_backbone=mode)
     eng = make_engine(sd)
+    if bool(getattr(eng, "siamese_backbone", True)) != mode:
+        raise ValueError("%s holds a %s model but make_engine built a %s engine (siamese_backbone=%r)"
+                         % (path, _MODE[mode], _MODE[not mode], not mode))
     if "optimizer" in extras and isinstance(extras["optimizer"], dict) and "momentum_buffer" in extras["optimizer"]:
         eng.load_optimizer_state_dict(extras["optimizer"])
     return eng, int(extras.get("iteration", 0))
+
+
+_MODE = {True: "two-backbone (siamese_backbone=True)", False: "shared-backbone (siamese_backbone=False)"}
 
 
 _C2_BRANCH = {"branch2a": ("conv1", "bn1"), "branch2b": ("conv2", "bn2"), "branch2c": ("conv3", "bn3"),
@@ -142,11 +177,11 @@ def translate_c2_resnet_name(name):
     return None if leaf is None else "layer%d.%d.%s.%s" % (stage - 1, block, conv, leaf)
 
 
-def load_c2_resnet(path, defaults, second_stage=None):
+def load_c2_resnet(path, defaults, second_stage=None, siamese_backbone=True):
     """A Detectron ResNet `.pkl` (dict of numpy blobs, optionally under "blobs"; pickled by Python 2: latin1) -> a full
     state_dict: the ResNet bodies of BOTH backbones come from the file, every other entry (FrozenBN running statistics —
     AffineChannel has none —, FPN, FCOS head, second stage) from `defaults`, as `DetectronCheckpointer.load` leaves the
-    model's own initialisation for what the file lacks."""
+    model's own initialisation for what the file lacks.  siamese_backbone=False: the shared-backbone model's keys only."""
     with open(path, "rb") as f:
         data = pickle.load(f, encoding="latin1")
     blobs = data["blobs"] if isinstance(data, dict) and "blobs" in data else data
@@ -155,7 +190,7 @@ def load_c2_resnet(path, defaults, second_stage=None):
         name = translate_c2_resnet_name(k)
         if name is not None:
             loaded[name] = torch.as_tensor(blobs[k])
-    shapes = spec.hot_path_shapes()
+    shapes = spec.hot_path_shapes(siamese_backbone)
     if second_stage or (second_stage is None and all(k in defaults for k in spec.box_head_shapes())):
         shapes.update(spec.box_head_shapes())
     body = OrderedDict((k, v) for k, v in shapes.items() if ".body." in k and not k.endswith(("running_mean", "running_var")))

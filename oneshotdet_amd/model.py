@@ -357,23 +357,29 @@ def run_proposals(head_out, img_h, img_w, pre_nms_top_n, post_nms_top_n, nms_thr
 
 class HotPathEngine(object):
     """Packed weights + forward of the hot path.  state_dict: reference-named fp32 tensors (any device; moved to
-    `device`).  dtype: torch.float32 (exact-fp32 MFMA) or torch.bfloat16 (bf16 MFMA, fp32 accumulate)."""
+    `device`).  dtype: torch.float32 (exact-fp32 MFMA) or torch.bfloat16 (bf16 MFMA, fp32 accumulate).
+    siamese_backbone (FEW_SHOT.SIAMESE_BACKBONE): True = the query has a backbone of its own (`supp_backbone.*`); False =
+    the query goes through the target's backbone (generalized_rcnn.py:274-275): ONE packed BackboneWeights serves both
+    branches (`supp_backbone` is the same object), and `supp_backbone.*` entries of the state_dict are dropped."""
 
-    def __init__(self, state_dict, dtype=torch.float32, device="cuda"):
+    def __init__(self, state_dict, dtype=torch.float32, device="cuda", siamese_backbone=True):
         if not torch.cuda.is_available():
             raise ops._lib.OsdError("HotPathEngine needs an MI355X: no GPU visible and there is no CPU fallback")
         ops._lib.load()
         self.device = torch.device(device)
         self.dtype = dtype
-        self.sd = {k: torch.as_tensor(v).to(self.device, torch.float32) for k, v in state_dict.items()}
-        missing = [k for k in spec.hot_path_shapes() if k not in self.sd]
+        self.siamese_backbone = bool(siamese_backbone)
+        self.sd = {k: torch.as_tensor(v).to(self.device, torch.float32) for k, v in state_dict.items()
+                   if self.siamese_backbone or not spec.is_query_backbone_key(k)}
+        missing = [k for k in spec.hot_path_shapes(self.siamese_backbone) if k not in self.sd]
         if missing:
             raise KeyError("state_dict is missing hot-path keys, e.g. %s" % missing[:3])
         self.repack()
 
     def repack(self):
         self.backbone = BackboneWeights(self.sd, "backbone.", self.dtype)
-        self.supp_backbone = BackboneWeights(self.sd, "supp_backbone.", self.dtype)
+        # shared mode: the query branch runs on the target's packed weights (nothing packed, copied or tuned twice)
+        self.supp_backbone = BackboneWeights(self.sd, "supp_backbone.", self.dtype) if self.siamese_backbone else self.backbone
         self.head = HeadWeights(self.sd, self.dtype)
         # second stage (SURVEY.md §8f #1): packed when the state_dict carries the reference's roi_heads.box.* entries
         self.box_head = None

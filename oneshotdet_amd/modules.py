@@ -178,11 +178,12 @@ class FCOSModule(nn.Module):
 class OneShotDetector(nn.Module):
     """GeneralizedRCNN (detector/generalized_rcnn.py:55-332) in eval mode: `backbone`, `supp_backbone`, `rpn` (and the
     `roi_heads.box.*` entries when present) under the reference's names, forward -> list[BoxList] with `scores` and
-    `labels` (= target_ids[i]) like the reference returns."""
+    `labels` (= target_ids[i]) like the reference returns.  siamese_backbone=False: the shared-backbone model
+    (FEW_SHOT.SIAMESE_BACKBONE False): no `supp_backbone`, the query goes through `backbone`."""
 
-    def __init__(self, state_dict, dtype=torch.float32, device="cuda"):
+    def __init__(self, state_dict, dtype=torch.float32, device="cuda", siamese_backbone=True):
         super(OneShotDetector, self).__init__()
-        self.engine = model.HotPathEngine(state_dict, dtype=dtype, device=device)
+        self.engine = model.HotPathEngine(state_dict, dtype=dtype, device=device, siamese_backbone=siamese_backbone)
         self.second_stage = self.engine.box_head is not None
 
     def state_dict(self, *a, **k):

@@ -145,20 +145,28 @@ def box_head_shapes(prefix="roi_heads.box."):
     return out
 
 
-def hot_path_shapes():
+def hot_path_shapes(siamese_backbone=True):
     """All state_dict entries of the hot path: target backbone, query backbone (separate weights,
-    generalized_rcnn.py:69-71), FCOS head."""
+    generalized_rcnn.py:69-71), FCOS head.  siamese_backbone=False (FEW_SHOT.SIAMESE_BACKBONE False, the reference's
+    default: the query goes through the target's `backbone`, generalized_rcnn.py:274-275): no `supp_backbone.*` entries."""
     out = backbone_shapes("backbone.")
-    out.update(backbone_shapes("supp_backbone."))
+    if siamese_backbone:
+        out.update(backbone_shapes("supp_backbone."))
     out.update(fcos_head_shapes())
     return out
 
 
-def full_model_shapes():
-    """Hot path + second-stage box head = every state_dict entry of the reference model under the config of record."""
-    out = hot_path_shapes()
+def full_model_shapes(siamese_backbone=True):
+    """Hot path + second-stage box head = every state_dict entry of the reference model under the config of record
+    (siamese_backbone: see hot_path_shapes)."""
+    out = hot_path_shapes(siamese_backbone)
     out.update(box_head_shapes())
     return out
+
+
+def is_query_backbone_key(key):
+    """An entry of the query branch's own backbone (two-backbone model only)."""
+    return key.startswith("supp_backbone.") or key.startswith("module.supp_backbone.")
 
 
 def is_frozen(key):

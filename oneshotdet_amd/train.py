@@ -11,6 +11,11 @@ Master weights are fp32 and live, like their gradients, in ONE flat buffer each,
 [Cout][R][S][Cin] order: the optimiser (elementwise), the weight-gradient kernel (atomics into that layout) and the
 bf16/fp32 packers all share it, and the gradient all-reduce is a handful of large contiguous RCCL calls.
 `state_dict()` converts back to the reference's OIHW names/shapes.
+
+siamese_backbone=False (FEW_SHOT.SIAMESE_BACKBONE False, generalized_rcnn.py:274-275): the query goes through the target's
+backbone.  There is then ONE set of backbone convs (master, momentum, packed forward and data-gradient copies, gradient
+buckets); both branches save their activations against it, and the weight-gradient launches add both branches' contributions
+into the one dW (BackwardPass._flush_shared_stage).
 """
 import math
 import os
@@ -77,7 +82,7 @@ class TConv(object):
 class TrainEngine(ForwardPass, BackwardPass, SecondStage, Update, State):
     def __init__(self, state_dict, dtype=torch.bfloat16, device="cuda", lr=0.0005, momentum=0.9, weight_decay=0.0001,
                  process_group=None, wgrad_side_stream=True, optimizer="fused", second_stage=False, ordered_wgrad=None,
-                 exchange_single_rank=False, grad_wire_dtype=None):
+                 exchange_single_rank=False, grad_wire_dtype=None, siamese_backbone=True):
         if not torch.cuda.is_available():
             raise ops._lib.OsdError("TrainEngine needs an MI355X: no GPU visible and there is no CPU fallback")
         ops._lib.load()
@@ -107,7 +112,16 @@ class TrainEngine(ForwardPass, BackwardPass, SecondStage, Update, State):
         self.split_levels = os.environ.get("OSD_SPLIT_LEVELS", "0") != "0"
         # the sum of the two towers' input gradients inside the cls tower's last data-gradient conv (A/B: OSD_NO_HEAD_SUM_FUSION=1)
         self.fuse_head_sum = os.environ.get("OSD_NO_HEAD_SUM_FUSION", "0") == "0"
-        sd = {k: torch.as_tensor(v).to(self.device, torch.float32) for k, v in state_dict.items()}
+        self.siamese_backbone = bool(siamese_backbone)
+        if not self.siamese_backbone:
+            # (target, query) branch prefixes: both run on the shared backbone's convs
+            self.BBS = ("backbone.", "backbone.")
+        self._shared_held = {}   # shared backbone: the query branch's queued weight gradients per stage (_flush_shared_stage)
+        sd = {k: torch.as_tensor(v).to(self.device, torch.float32) for k, v in state_dict.items()
+              if self.siamese_backbone or not spec.is_query_backbone_key(k)}
+        missing = [k for k in spec.hot_path_shapes(self.siamese_backbone) if k not in sd]
+        if missing:
+            raise KeyError("state_dict is missing hot-path keys (siamese_backbone=%r), e.g. %s" % (self.siamese_backbone, missing[:3]))
         self._frozen_sd = sd
         self.convs = {}          # name -> TConv
         self.extra = {}          # name -> (param view, grad view) for GN affine and Scale parameters
@@ -117,7 +131,7 @@ class TrainEngine(ForwardPass, BackwardPass, SecondStage, Update, State):
         from . import model as _model
         self._fused_l1 = {}      # backbone prefix -> conv3 + downsample of the frozen layer1.0 as one packed 1x1 conv
         if _model.FUSE_DOWNSAMPLE and dtype == torch.bfloat16:       # see model.BackboneWeights: bf16 engines only
-            for bb in self.BBS:
+            for bb in dict.fromkeys(self.BBS):
                 if (bb + "body.layer1.0.downsample.0.weight") in sd:
                     self._fused_l1[bb] = _model.pack_conv3_downsample(sd, bb + "body.layer1.0.", dtype)
         # gradient exchange overlapped with backward (no-op with one rank): buckets in the order they become final; the
@@ -227,7 +241,7 @@ class TrainEngine(ForwardPass, BackwardPass, SecondStage, Update, State):
         return c
 
     def _build(self, sd):
-        for bb in ("backbone.", "supp_backbone."):
+        for bb in dict.fromkeys(self.BBS):
             b = bb + "body."
             self._add_conv(b + "stem.conv1", sd, bn=b + "stem.bn1", trainable=False)
             for si, nblocks in enumerate(spec.STAGE_BLOCKS):
@@ -357,7 +371,7 @@ class TrainEngine(ForwardPass, BackwardPass, SecondStage, Update, State):
         return self.extra[name + ".weight"], self.extra[name + ".bias"]
 
     # ------------------------------------------------------------------------------------------------ forward
-    BBS = ("backbone.", "supp_backbone.")
+    BBS = ("backbone.", "supp_backbone.")        # (target, query) branch prefixes; shared backbone: ("backbone.", "backbone.")
 
     TOWERS = ("cls_tower", "bbox_tower")
 

@@ -70,6 +70,30 @@ class BackwardPass(object):
                          for c, x, dy, stride, pad in part]
                 self._on_wstream(lambda items=items: ops.conv2d_wgrad_mixed(items), items, which)
 
+    def _flush_shared_stage(self, sname, which0):
+        """Shared backbone (siamese_backbone=False): the target and the query branch add into ONE dW per conv.  A one-split
+        segment of a wgrad launch may add with a plain load + store (owner mode), and the launch can rule that out only among
+        its own segments — so the two branches' weight gradients of a stage never go out as concurrent launches: they are
+        queued into ONE stage flush on the target's weight-gradient stream (chunks of > 24 segments follow each other on that
+        stream).  The query-only backward (which0 = 1: its own stream beside the target's, enqueued first) holds its stage's
+        queue with an event on its stream; the target's flush of that stage waits for the event and takes the held items
+        along.  Waiting for it also orders the stage's update (which waits for this weight-gradient stream) after the
+        query branch's data-gradient convs that read the packed weights it rewrites.  -> True if the stage went out."""
+        q, self._wqs[0] = self._wqs[0], []
+        if which0 == 1:
+            ev = torch.cuda.Event()
+            ev.record()
+            self._shared_held[sname] = (q, ev)
+            return False
+        held = self._shared_held.pop(sname, None)
+        if held is not None:
+            ws = self._wstream_of(0) or streams.current()
+            ws.wait_event(held[1])
+            q = held[0] + q
+        self._wqs[0] = q
+        self._flush_wgrads(0, 0)
+        return True
+
     def _wgrad_grouped(self, c, pairs, which=0, g=None):
         self._on_wstream(lambda: ops.conv2d_wgrad_grouped(pairs, c.gw, c.r, c.s, 1, c.r // 2, c.cout, scale=c.bn_scale,
                                                           db=c.gb if c.has_bias else None, g=g), (pairs, g), which)
@@ -253,13 +277,14 @@ class BackwardPass(object):
         bbs = [c["bb"] for c in ctxs]
         nb = len(ctxs)
         self._wqs = [[] for _ in ctxs]
+        shared = not self.siamese_backbone         # both branches' weight gradients go into one queue (_flush_shared_stage)
 
         def col(key):
             return [c[key] for c in ctxs]
 
         def W(name, xs, dys, stride=1, pad=0):
             for j in range(nb):
-                self._wqs[j].append((cv[bbs[j] + name], xs[j], dys[j], stride, pad))
+                self._wqs[0 if shared else j].append((cv[bbs[j] + name], xs[j], dys[j], stride, pad))
 
         def D(name, dys, residuals=None, masks=None):
             """Data gradient of a stride-1 conv: the forward kernel on dy with flipped/transposed weights."""
@@ -317,7 +342,10 @@ class BackwardPass(object):
             sname = ("layer4+fpn" if stage == "layer4" else stage) if p.endswith(".0.") else None
 
             def stage_done():
-                for j in range(nb):
+                if shared:
+                    if self._flush_shared_stage(sname, which0):
+                        self._bucket_ready(bbs[0].rstrip(".") + "." + sname, 0)
+                for j in range(0 if shared else nb):
                     self._flush_wgrads(j, which0 + j)
                     self._bucket_ready(bbs[j].rstrip(".") + "." + sname, which0 + j)
                 if which0 == 0:
@@ -340,7 +368,12 @@ class BackwardPass(object):
             if sname is not None:       # first block of its stage done (its data-gradient convs included): the stage's
                 stage_done()            # weight gradients go out, then its gradients are final and nothing enqueued
         for j in range(nb):             # later reads its packed weights
-            self._flush_wgrads(j, which0 + j)
+            if shared:
+                assert not self._wqs[j], "shared backbone: weight gradients queued outside a stage"
+            else:
+                self._flush_wgrads(j, which0 + j)
+        if shared and which0 == 0:
+            assert not self._shared_held, "shared backbone: the query branch's weight gradients of %s were not flushed" % list(self._shared_held)
         self._wqs = None
         if which0 == 0:
             self._release_held_wgrads(self.tower_wgrad_at)      # whatever was not released on the way
