@@ -1,12 +1,15 @@
 """One-shot detection end to end on an MI355X with this build, the way a user of RyanXLi/OneshotDet would call it:
 
     python examples/detect.py [--checkpoint model_0040000.pth | --c2 R-50.pkl] [--dtype bf16|f32] [--second-stage]
-                              [--shared-backbone]
+                              [--shared-backbone] [--no-supp-roialign]
+    python examples/detect.py --checkpoint model_0930.pth --shared-backbone --no-supp-roialign      # the 0930 model
 
   * weights: a reference `.pth` (utils/checkpoint.py format), a Detectron ResNet `.pkl` for the backbones, or — there is no
     network here — the deterministic synthetic weights the tests use;
   * model: a checkpoint is run as the model that wrote it (shared backbone when it holds no `supp_backbone.*`);
-    --shared-backbone (FEW_SHOT.SIAMESE_BACKBONE False) for the other sources;
+    --shared-backbone (FEW_SHOT.SIAMESE_BACKBONE False) for the other sources.  --no-supp-roialign (FEW_SHOT.SUPP_ROIALIGN False)
+    pools the query pyramid by global average: the reference's default config and configs/fcos/0930fixed_thres.yaml need it
+    with --shared-backbone, and nothing in a weights file says so (a training checkpoint of this build records it);
   * inputs: lists of CHW BGR-minus-mean images of different sizes for targets and queries; `to_image_list` pads them to
     a common /32 size and keeps the true sizes (data/collate_batch.py + structures/image_list.py of the reference);
   * output: one BoxList per target image (boxes, scores, labels = the query's class id), like `GeneralizedRCNN.forward`.
@@ -28,8 +31,10 @@ def main():
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "f32"])
     ap.add_argument("--first-stage-only", action="store_true")
     ap.add_argument("--shared-backbone", action="store_true", help="one backbone for target and query (SIAMESE_BACKBONE False)")
+    ap.add_argument("--no-supp-roialign", action="store_true", help="pool the query pyramid by global average (SUPP_ROIALIGN False)")
     args = ap.parse_args()
     siamese = not args.shared_backbone
+    roialign = not args.no_supp_roialign
     if args.checkpoint:
         siamese = checkpoint.has_query_backbone(args.checkpoint)       # the file's own mode
     shapes = spec.hot_path_shapes(siamese) if args.first_stage_only else spec.full_model_shapes(siamese)
@@ -38,13 +43,17 @@ def main():
         sd, extras = checkpoint.load_checkpoint(args.checkpoint, defaults=defaults, siamese_backbone=siamese)
         print("loaded", args.checkpoint, "(%s backbone)" % ("siamese" if siamese else "shared"),
               {k: v for k, v in extras.items() if not isinstance(v, dict)})
+        if "supp_roialign" in extras and bool(extras["supp_roialign"]) != roialign:
+            raise SystemExit("%s was trained with supp_roialign=%r: %s --no-supp-roialign" % (
+                args.checkpoint, bool(extras["supp_roialign"]), "drop" if roialign is False else "add"))
     elif args.c2:
         sd = checkpoint.load_c2_resnet(args.c2, defaults, siamese_backbone=siamese)
         print("backbones initialised from", args.c2)
     else:
         sd = defaults
         print("synthetic weights (no checkpoint given)")
-    det = modules.OneShotDetector(sd, dtype=torch.bfloat16 if args.dtype == "bf16" else torch.float32, siamese_backbone=siamese)
+    det = modules.OneShotDetector(sd, dtype=torch.bfloat16 if args.dtype == "bf16" else torch.float32, siamese_backbone=siamese,
+                                  supp_roialign=roialign)
     # two targets and two queries of different sizes
     targets = [torch.from_numpy(synth.make_images("ex.t%d" % i, 1, h, w)[0]) for i, (h, w) in enumerate([(480, 640), (512, 384)])]
     queries = [torch.from_numpy(synth.make_images("ex.q%d" % i, 1, h, w)[0]) for i, (h, w) in enumerate([(127, 127), (96, 160)])]

@@ -219,6 +219,17 @@ int osd_shot_mean(const float* x, float* y, int b, int shots, int c, void* strea
 int osd_query_pool_levels(int n_levels, const void* const* xs, const int32_t* hs, const int32_t* ws, const float* scales,
                           const float* rois, int batch, int shots, int c, int sampling_ratio, float* const* ys, int dtype,
                           void* stream);
+/* FEW_SHOT.SUPP_ROIALIGN False: the query pooling by global average instead (generalized_rcnn.py:87-94, 302-303:
+ * nn.AdaptiveAvgPool2d((1, 1)) of every query feature map, i.e. the mean of the WHOLE map, padding included) followed by
+ * batch_pooling (:100-104), for all FPN levels in two launches.  xs[l]: NHWC [batch * shots][hs[l]][ws[l]][c] `dtype`; ys[l]
+ * [batch][c] fp32 = (sum_k (sum_hw x[b * shots + k]) / (hs[l] * ws[l])) / shots, accumulated in fp32.  Deterministic: every sum is
+ * taken in an order fixed by (hs[l], ws[l], shots) (no atomics; batch size, stream and timing do not change a bit).  xs / ys / hs /
+ * ws are HOST arrays of n_levels <= 8 entries; xs, ys and workspace 16-byte aligned; c % 8 == 0 (else OSD_ERR_UNSUPPORTED).
+ * workspace: caller-owned fp32 scratch of osd_query_avgpool_workspace_bytes(n_levels, hs, ws, batch * shots, c) bytes (per-chunk
+ * partial sums; no initialisation needed).  The workspace query returns a negative OSD_ERR_* for a shape the kernels refuse. */
+int64_t osd_query_avgpool_workspace_bytes(int n_levels, const int32_t* hs, const int32_t* ws, int maps, int c);
+int osd_query_avgpool_levels(int n_levels, const void* const* xs, const int32_t* hs, const int32_t* ws, int batch, int shots,
+                             int c, float* const* ys, float* workspace, int64_t workspace_bytes, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Query<->target correlation: y[n,h,w,c] = x[n,h,w,c] * q[n,c] (depthwise cross-correlation with a 1x1 query kernel),
@@ -418,6 +429,12 @@ int osd_shot_mean_bwd(const float* gy, float* gx, int b, int shots, int c, void*
 int osd_query_pool_levels_bwd(int n_levels, const float* const* dqs, const int32_t* hs, const int32_t* ws, const float* scales,
                               const float* rois, int batch, int shots, int c, int sampling_ratio, float* gx32, void* const* outs,
                               int dtype, void* stream);
+/* backward of osd_query_avgpool_levels (autograd of AdaptiveAvgPool2d + batch_pooling in the reference): outs[l]
+ * [batch * shots][hs[l]][ws[l]][c] `dtype` = dqs[l][n / shots][c] / (hs[l] * ws[l]) / shots at every pixel of map n (fp32, then
+ * cast as osd_cast_f32 casts), all levels in one write-only launch, no scratch.  dqs[l] [batch][c] fp32.  Same conventions as the
+ * forward. */
+int osd_query_avgpool_levels_bwd(int n_levels, const float* const* dqs, const int32_t* hs, const int32_t* ws, int batch,
+                                 int shots, int c, void* const* outs, int dtype, void* stream);
 int osd_cast_f32(const float* src, void* dst, int64_t numel, int dtype, void* stream);
 /* Gradient bucket on its way to (to_wire = 1: fp32 src -> bf16 dst) or back from (to_wire = 0: bf16 src -> fp32 dst) a
  * half-width all-reduce (DDP's bf16 compression hook is the reference-side equivalent; tools/train_net.py:83-88 itself

@@ -49,6 +49,9 @@ SIGNATURES = {
     "osd_shot_mean": (_i, [_p, _p, _i, _i, _i, _p]),
     "osd_query_pool_levels": (_i, [_i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _i, _p]),
     "osd_query_pool_levels_bwd": (_i, [_i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _i, _p]),
+    "osd_query_avgpool_workspace_bytes": (_i64, [_i, _p, _p, _i, _i]),
+    "osd_query_avgpool_levels": (_i, [_i, _p, _p, _p, _i, _i, _i, _p, _p, _i64, _i, _p]),
+    "osd_query_avgpool_levels_bwd": (_i, [_i, _p, _p, _p, _i, _i, _i, _p, _i, _p]),
     "osd_correlate_fwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _p]),
     "osd_correlate_levels": (_i, [_i, _p, _p, _p, _p, _i, _i, _i, _p]),
     "osd_correlate_bwd_query_levels": (_i, [_i, _p, _p, _p, _p, _i, _i, _i, _p]),

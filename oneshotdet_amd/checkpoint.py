@@ -10,6 +10,8 @@ suffix alignment then fills BOTH backbones (every `*.body.layer1.0.conv1.weight`
 siamese_backbone (FEW_SHOT.SIAMESE_BACKBONE): True = the two-backbone model (a shared-backbone file fills `supp_backbone.*` from
 `backbone.*` by that suffix match, as the reference does); False = the shared-backbone model, whose key set has no
 `supp_backbone.*` (a two-backbone file's query backbone is ignored, as the reference ignores keys its model does not have).
+supp_roialign (FEW_SHOT.SUPP_ROIALIGN) changes no key: the query pooling has no weights, so loading is the same in both modes;
+training checkpoints record it, and `resume_training` refuses to continue a run in the other mode.
 """
 import os
 import pickle
@@ -109,17 +111,26 @@ def save_checkpoint(path, state_dict, tag_last=True, **extras):
 def save_training_checkpoint(path, engine, iteration, tag_last=True):
     """utils/checkpoint.py:33-50 as the trainer calls it (engine/trainer.py:111-119): model + optimizer + iteration.
     `optimizer` holds TrainEngine.optimizer_state_dict() (momentum buffers under reference names, steps taken, lr);
-    `siamese_backbone` the engine's mode (a shared engine writes no `supp_backbone.*`)."""
+    `siamese_backbone` the engine's mode (a shared engine writes no `supp_backbone.*`); `supp_roialign` its query pooling (the
+    only record of it: the pooling has no weights)."""
     return save_checkpoint(path, engine.state_dict(), tag_last=tag_last, optimizer=engine.optimizer_state_dict(),
-                           iteration=int(iteration), siamese_backbone=bool(getattr(engine, "siamese_backbone", True)))
+                           iteration=int(iteration), siamese_backbone=bool(getattr(engine, "siamese_backbone", True)),
+                           supp_roialign=bool(getattr(engine, "supp_roialign", True)))
 
 
-def resume_training(path, make_engine, siamese_backbone=None):
+def resume_training(path, make_engine, siamese_backbone=None, supp_roialign=None):
     """Load a checkpoint written by save_training_checkpoint: make_engine(state_dict) -> TrainEngine; its momentum and
     step count are restored.  Returns (engine, iteration).  The file's mode (recorded by save_training_checkpoint; for
     older files: whether it holds `supp_backbone.*`) must be the engine's: a resumed run never ties or unties weights
-    behind the caller's back.  siamese_backbone: the mode the caller expects (None: whatever the file holds)."""
+    behind the caller's back.  siamese_backbone: the mode the caller expects (None: whatever the file holds).  The same
+    for the query pooling: supp_roialign is the caller's expectation, the file's record (True when it has none, the
+    files written before the option existed) must match it and the engine's."""
     data = _read(path)
+    pool = data.get("supp_roialign")
+    pool = True if pool is None else bool(pool)
+    if supp_roialign is not None and bool(supp_roialign) != pool:
+        raise ValueError("%s was trained with %s; resuming it with %s would continue another model: build the engine with "
+                         "supp_roialign=%r" % (path, _POOL[pool], _POOL[bool(supp_roialign)], pool))
     mode = data.get("siamese_backbone")
     mode = has_query_backbone(data["model"]) if mode is None else bool(mode)
     if siamese_backbone is not None and bool(siamese_backbone) != mode:
@@ -132,12 +143,16 @@ def resume_training(path, make_engine, siamese_backbone=None):
     if bool(getattr(eng, "siamese_backbone", True)) != mode:
         raise ValueError("%s holds a %s model but make_engine built a %s engine (siamese_backbone=%r)"
                          % (path, _MODE[mode], _MODE[not mode], not mode))
+    if bool(getattr(eng, "supp_roialign", True)) != pool:
+        raise ValueError("%s was trained with %s but make_engine built an engine with %s (supp_roialign=%r)"
+                         % (path, _POOL[pool], _POOL[not pool], not pool))
     if "optimizer" in extras and isinstance(extras["optimizer"], dict) and "momentum_buffer" in extras["optimizer"]:
         eng.load_optimizer_state_dict(extras["optimizer"])
     return eng, int(extras.get("iteration", 0))
 
 
 _MODE = {True: "two-backbone (siamese_backbone=True)", False: "shared-backbone (siamese_backbone=False)"}
+_POOL = {True: "ROIAlign query pooling (supp_roialign=True)", False: "global-average query pooling (supp_roialign=False)"}
 
 
 _C2_BRANCH = {"branch2a": ("conv1", "bn1"), "branch2b": ("conv2", "bn2"), "branch2c": ("conv3", "bn3"),

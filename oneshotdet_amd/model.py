@@ -224,8 +224,12 @@ def image_sizes_dev(image_sizes, device):
     return _SIZE_CACHE[key]
 
 
-def run_query_pool(qfeats, q_sizes, batch):
-    """SuppAlignLayer (generalized_rcnn.py:20-52) + batch_pooling (:100-104) -> 5 x [B, C] fp32."""
+def run_query_pool(qfeats, q_sizes, batch, supp_roialign=True):
+    """SuppAlignLayer (generalized_rcnn.py:20-52) + batch_pooling (:100-104) -> 5 x [B, C] fp32.  supp_roialign=False
+    (FEW_SHOT.SUPP_ROIALIGN False): nn.AdaptiveAvgPool2d((1, 1)) instead (:87-94, 302-303), the mean of each whole map, padding
+    included, so q_sizes plays no part."""
+    if not supp_roialign:
+        return ops.query_avgpool_levels(qfeats, batch)
     rois = whole_image_rois(q_sizes, qfeats[0].device)
     if ops.QUERY_POOL_LEVELS and len(qfeats) <= 8:
         return ops.query_pool_levels(qfeats, rois, spec.POOLER_SCALES, batch, spec.POOLER_SAMPLING_RATIO)
@@ -360,15 +364,18 @@ class HotPathEngine(object):
     `device`).  dtype: torch.float32 (exact-fp32 MFMA) or torch.bfloat16 (bf16 MFMA, fp32 accumulate).
     siamese_backbone (FEW_SHOT.SIAMESE_BACKBONE): True = the query has a backbone of its own (`supp_backbone.*`); False =
     the query goes through the target's backbone (generalized_rcnn.py:274-275): ONE packed BackboneWeights serves both
-    branches (`supp_backbone` is the same object), and `supp_backbone.*` entries of the state_dict are dropped."""
+    branches (`supp_backbone` is the same object), and `supp_backbone.*` entries of the state_dict are dropped.
+    supp_roialign (FEW_SHOT.SUPP_ROIALIGN): True = the query pyramid is pooled by a 1 x 1 ROIAlign of each query's box; False =
+    by its global average (run_query_pool).  The pooling has no weights: a state_dict does not tell the two apart."""
 
-    def __init__(self, state_dict, dtype=torch.float32, device="cuda", siamese_backbone=True):
+    def __init__(self, state_dict, dtype=torch.float32, device="cuda", siamese_backbone=True, supp_roialign=True):
         if not torch.cuda.is_available():
             raise ops._lib.OsdError("HotPathEngine needs an MI355X: no GPU visible and there is no CPU fallback")
         ops._lib.load()
         self.device = torch.device(device)
         self.dtype = dtype
         self.siamese_backbone = bool(siamese_backbone)
+        self.supp_roialign = bool(supp_roialign)
         self.sd = {k: torch.as_tensor(v).to(self.device, torch.float32) for k, v in state_dict.items()
                    if self.siamese_backbone or not spec.is_query_backbone_key(k)}
         missing = [k for k in spec.hot_path_shapes(self.siamese_backbone) if k not in self.sd]
@@ -407,19 +414,19 @@ class HotPathEngine(object):
         q_sizes = [tuple(queries.shape[-2:])] * queries.shape[0] if query_sizes is None else list(query_sizes)
         if concurrent and LOCKSTEP:
             feats, qfeats = run_backbones(self.backbone, self.supp_backbone, images, queries, self.dtype)
-            pooled = run_query_pool(qfeats, q_sizes, batch)
+            pooled = run_query_pool(qfeats, q_sizes, batch, self.supp_roialign)
         elif concurrent:
             main, side = _streams.current(), self.side_streams()[0]
             side.wait_stream(main)
             with _streams.on(side):
                 qfeats = run_backbone(self.supp_backbone, queries, self.dtype)
-                pooled = run_query_pool(qfeats, q_sizes, batch)
+                pooled = run_query_pool(qfeats, q_sizes, batch, self.supp_roialign)
             feats = run_backbone(self.backbone, images, self.dtype)
             main.wait_stream(side)
         else:
             feats = run_backbone(self.backbone, images, self.dtype)
             qfeats = run_backbone(self.supp_backbone, queries, self.dtype)
-            pooled = run_query_pool(qfeats, q_sizes, batch)
+            pooled = run_query_pool(qfeats, q_sizes, batch, self.supp_roialign)
         combined = run_correlate(feats, pooled)
         return feats, qfeats, pooled, combined
 

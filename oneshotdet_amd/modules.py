@@ -179,11 +179,13 @@ class OneShotDetector(nn.Module):
     """GeneralizedRCNN (detector/generalized_rcnn.py:55-332) in eval mode: `backbone`, `supp_backbone`, `rpn` (and the
     `roi_heads.box.*` entries when present) under the reference's names, forward -> list[BoxList] with `scores` and
     `labels` (= target_ids[i]) like the reference returns.  siamese_backbone=False: the shared-backbone model
-    (FEW_SHOT.SIAMESE_BACKBONE False): no `supp_backbone`, the query goes through `backbone`."""
+    (FEW_SHOT.SIAMESE_BACKBONE False): no `supp_backbone`, the query goes through `backbone`.  supp_roialign=False
+    (FEW_SHOT.SUPP_ROIALIGN False): the query pyramid is pooled by global average instead of the 1 x 1 ROIAlign."""
 
-    def __init__(self, state_dict, dtype=torch.float32, device="cuda", siamese_backbone=True):
+    def __init__(self, state_dict, dtype=torch.float32, device="cuda", siamese_backbone=True, supp_roialign=True):
         super(OneShotDetector, self).__init__()
-        self.engine = model.HotPathEngine(state_dict, dtype=dtype, device=device, siamese_backbone=siamese_backbone)
+        self.engine = model.HotPathEngine(state_dict, dtype=dtype, device=device, siamese_backbone=siamese_backbone,
+                                          supp_roialign=supp_roialign)
         self.second_stage = self.engine.box_head is not None
 
     def state_dict(self, *a, **k):

@@ -525,6 +525,49 @@ def query_pool_levels_bwd(dqs, rois, shapes, scales, shots, sampling_ratio, dtyp
     return outs
 
 
+def query_avgpool_levels(feats, batch):
+    """FEW_SHOT.SUPP_ROIALIGN False: nn.AdaptiveAvgPool2d((1, 1)) of every query feature map (the mean of the whole map, padding
+    included; generalized_rcnn.py:87-94, 302-303) + the mean over the shots of a target image (:100-104) for ALL FPN levels in two
+    launches: feats[l] NHWC [batch * shots, h, w, C] -> [B, C] fp32 per level (views of one buffer).  Bit-reproducible, and image
+    i's vector does not depend on the batch it is in."""
+    _chk_dev(*feats)
+    k = len(feats)
+    r, c = feats[0].shape[0], feats[0].shape[-1]
+    assert r % batch == 0 and all(f.shape[0] == r and f.shape[-1] == c for f in feats)
+    feats = [f.contiguous() for f in feats]
+    hs, ws = (C.c_int32 * k)(*[f.shape[1] for f in feats]), (C.c_int32 * k)(*[f.shape[2] for f in feats])
+    nbytes = _lib.load().osd_query_avgpool_workspace_bytes(k, hs, ws, r, c)
+    _lib.check(min(int(nbytes), 0), "osd_query_avgpool_workspace_bytes")
+    scratch = torch.empty((max(nbytes // 4, 4),), device=feats[0].device, dtype=torch.float32)
+    flat = torch.empty((k, batch, c), device=feats[0].device, dtype=torch.float32)
+    ys = [flat[l] for l in range(k)]
+    _lib.call("osd_query_avgpool_levels", k, _ptr_array(feats), hs, ws, batch, r // batch, c, _ptr_array(ys), _p(scratch), nbytes,
+              _dt(feats[0]), _stream())
+    _rec("query_avgpool", xs=feats, batch=batch, outs=ys)
+    return ys
+
+
+def query_avgpool_levels_bwd(dqs, shapes, shots, dtype):
+    """Backward of query_avgpool_levels: dqs[l] [B, C] fp32 -> the gradient of the query feature maps, [B * shots, h, w, C] `dtype`
+    per level (views of one buffer) = dqs[l][n // shots] / (h * w) / shots at every pixel of map n, in one launch."""
+    _chk_dev(*dqs)
+    k = len(dqs)
+    b, c = dqs[0].shape
+    r = b * shots
+    dqs = [d.contiguous() for d in dqs]
+    assert all(tuple(sh) == (r, sh[1], sh[2], c) for sh in shapes)
+    sizes = [r * h * w * c for (_, h, w, _) in shapes]
+    flat = torch.empty((sum(sizes),), device=dqs[0].device, dtype=dtype)
+    outs, off = [], 0
+    for sh, n in zip(shapes, sizes):
+        outs.append(flat[off:off + n].view(tuple(sh)))
+        off += n
+    _lib.call("osd_query_avgpool_levels_bwd", k, _ptr_array(dqs), (C.c_int32 * k)(*[sh[1] for sh in shapes]),
+              (C.c_int32 * k)(*[sh[2] for sh in shapes]), b, shots, c, _ptr_array(outs), _dt(flat), _stream())
+    _rec("query_avgpool_bwd", dqs=dqs, shots=shots, outs=outs)
+    return outs
+
+
 def correlate(x, q, out=None):
     """x NHWC [N,H,W,C] * q [N,C] fp32 (broadcast over H, W)."""
     _chk_dev(x, q)

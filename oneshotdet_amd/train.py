@@ -16,6 +16,9 @@ siamese_backbone=False (FEW_SHOT.SIAMESE_BACKBONE False, generalized_rcnn.py:274
 backbone.  There is then ONE set of backbone convs (master, momentum, packed forward and data-gradient copies, gradient
 buckets); both branches save their activations against it, and the weight-gradient launches add both branches' contributions
 into the one dW (BackwardPass._flush_shared_stage).
+
+supp_roialign=False (FEW_SHOT.SUPP_ROIALIGN False, generalized_rcnn.py:87-94, 302-303): the query pyramid is pooled by global
+average (ops.query_avgpool_levels) instead of the 1 x 1 ROIAlign of each query's box, in the forward and in the pooling backward.
 """
 import math
 import os
@@ -82,7 +85,7 @@ class TConv(object):
 class TrainEngine(ForwardPass, BackwardPass, SecondStage, Update, State):
     def __init__(self, state_dict, dtype=torch.bfloat16, device="cuda", lr=0.0005, momentum=0.9, weight_decay=0.0001,
                  process_group=None, wgrad_side_stream=True, optimizer="fused", second_stage=False, ordered_wgrad=None,
-                 exchange_single_rank=False, grad_wire_dtype=None, siamese_backbone=True):
+                 exchange_single_rank=False, grad_wire_dtype=None, siamese_backbone=True, supp_roialign=True):
         if not torch.cuda.is_available():
             raise ops._lib.OsdError("TrainEngine needs an MI355X: no GPU visible and there is no CPU fallback")
         ops._lib.load()
@@ -113,6 +116,7 @@ class TrainEngine(ForwardPass, BackwardPass, SecondStage, Update, State):
         # the sum of the two towers' input gradients inside the cls tower's last data-gradient conv (A/B: OSD_NO_HEAD_SUM_FUSION=1)
         self.fuse_head_sum = os.environ.get("OSD_NO_HEAD_SUM_FUSION", "0") == "0"
         self.siamese_backbone = bool(siamese_backbone)
+        self.supp_roialign = bool(supp_roialign)
         if not self.siamese_backbone:
             # (target, query) branch prefixes: both run on the shared backbone's convs
             self.BBS = ("backbone.", "backbone.")
@@ -426,13 +430,15 @@ class TrainEngine(ForwardPass, BackwardPass, SecondStage, Update, State):
         batch = images.shape[0]
         shots = queries.shape[0] // batch
         q_sizes = [tuple(queries.shape[-2:])] * queries.shape[0] if query_sizes is None else [tuple(v) for v in query_sizes]
-        rois = model.whole_image_rois(q_sizes, self.device)
+        rois = model.whole_image_rois(q_sizes, self.device) if self.supp_roialign else None
         # ---- forward: both backbones in lockstep (one launch per layer), query pooling, correlation, head
         lock = self.lockstep
         side = s1 if s1 is not None else main
         af = join_previous if deferred is not None else None
 
         def pool(qf):
+            if not self.supp_roialign:      # global average (generalized_rcnn.py:302-303): all levels in two launches
+                return ops.query_avgpool_levels(qf, batch)
             if ops.QUERY_POOL_LEVELS and len(qf) <= 8:      # all levels in one launch (round 6: 10 launches -> 1)
                 return ops.query_pool_levels(qf, rois, spec.POOLER_SCALES, batch, spec.POOLER_SAMPLING_RATIO)
             out = []
@@ -495,7 +501,9 @@ class TrainEngine(ForwardPass, BackwardPass, SecondStage, Update, State):
             self.box_losses, gx, gqs = box_out
         with streams.on(side):      # the query branch's small pooling-backward chain beside d feat
             dQ = []
-            if ops.QUERY_POOL_LEVELS and len(dq) <= 8:      # all levels in three launches (round 6: 20 launches + 5 memsets before)
+            if not self.supp_roialign:      # the average's gradient: every pixel of a map gets dq / (h * w) / shots, one launch
+                dQ = ops.query_avgpool_levels_bwd(dq, [tuple(qf.shape) for qf in qfeats], shots, self.dtype)
+            elif ops.QUERY_POOL_LEVELS and len(dq) <= 8:      # all levels in three launches (round 6: 20 launches + 5 memsets before)
                 dQ = ops.query_pool_levels_bwd(dq, rois, [tuple(qf.shape) for qf in qfeats], spec.POOLER_SCALES, shots,
                                                spec.POOLER_SAMPLING_RATIO, self.dtype)
             else:
