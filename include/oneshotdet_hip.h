@@ -57,7 +57,7 @@ typedef struct osd_conv_desc {
   int32_t dtype;          /* OSD_F32 | OSD_BF16: element type of x, w, res, y */
   int32_t n, h, w;        /* input batch and spatial size (as stored) */
   int32_t cin;            /* K elements per filter tap (multiple of 16 (f32) / 32 (bf16)) */
-  int32_t in_stride_n, in_stride_h, in_stride_w; /* input strides in ELEMENTS (in_stride_w = cin for dense NHWC) */
+  int32_t in_stride_n, in_stride_h, in_stride_w; /* input strides in ELEMENTS (in_stride_w = cin for dense NHWC; see "Strides" below) */
   int32_t ho, wo, cout;   /* output spatial size and channels (cout multiple of 4) */
   int32_t r, s;           /* filter taps */
   int32_t stride_h, stride_w, pad_h, pad_w;
@@ -83,6 +83,15 @@ typedef struct osd_conv_desc {
                              no state between calls.  osd_conv2d_wgrad_mixed reads it from descs[0]. */
   int64_t ordered_ws_bytes;
 } osd_conv_desc;
+
+/* Strides (input strides keep 16-byte alignment; the stem's packed image excepted).  osd_conv2d_fwd honours in_stride_n / _h / _w
+ * (a channel slice of a wider tensor, padded rows, gaps between images) on the LDS-DMA and register-staged kernels (algo 0, 1 - 32
+ * except tile 6, 33 - 36) and the deep-ring tiles (57 - 60); conv_sp (tile 6: algos 7 / 15 / 23 / 31), the prediction-conv kernel
+ * (51) and the pixel-stationary 1x1 kernel (49 / 50) read dense NHWC input only and return OSD_ERR_UNSUPPORTED for any other input
+ * stride.  Every forward kernel honours out_stride (it writes channels [0, cout) of each output pixel and nothing else) and
+ * res_stride.  The _grouped / _multi forms take dense tensors (their ns / hs / ws arrays give the geometry; the input strides of d
+ * are not read).  The weight-gradient entries need dense input — osd_conv2d_wgrad, _batched and _mixed return
+ * OSD_ERR_UNSUPPORTED otherwise — and honour out_stride as the pixel stride of dy. */
 
 /* second pixel source of a 1x1 convolution (osd_conv2d_fwd): dense NHWC [n][h][w][cin2]; output pixel (ho, wo) reads
  * x[n][ho * stride][wo * stride].  cin and cin2 multiples of 64.  w2 (nullable): the second part's own packed weights
@@ -335,7 +344,7 @@ int osd_pack_conv_weight_dgrad(const float* w, const float* scale, void* dst, in
  * needs more than ordered_ws_bytes (workgroups x (tile + tile rows) x 4; 1 GiB covers every launch of the training step)
  * fails with OSD_ERR_WORKSPACE.  The buffer must not be shared by launches that run concurrently. */
 /* dW[cout][r][s][cin] (fp32, ACCUMULATED with atomics: zero it first) += sum over pixels dy[m][co] * x[m@tap][ci].
- * d describes the FORWARD conv (x geometry, strides, pads, cout, out_stride = pixel stride of dy); scale (nullable) is a
+ * d describes the FORWARD conv (x geometry: dense NHWC, strides, pads, cout, out_stride = pixel stride of dy); scale (nullable) is a
  * per-Cout factor applied to the contribution (the folded FrozenBN scale); db (nullable, fp32 [cout], accumulated) also
  * receives the bias gradient sum_m dy[m][co] from the same pass over dy.
  * d->algo: 0 = default, else 1 + variant + 8 * split_target_code.  Variants 0..3: 128 x 128 channel tile, pixels per

@@ -469,9 +469,10 @@ int osd_conv_sp_launch(const ConvKParams& pin, hipStream_t stream, bool general_
   // any width: dense maps (Wo == W, Ho == H) under 2 GiB.  The padded-image form needs W in 64 / 128 / 256 (tiles start at x = 0
   // and hold whole lines); every other width — or all of them with general_width — runs the consecutive-rows form (GENW)
   bool genw = general_width;
-  auto ok = [&](int w, int wo, int h, int ho, int m, int sh) {
+  // dense: pixel m of the launch is read at m * Cin, across image borders too (in_stride_n = h * w * cin; gaps are refused)
+  auto ok = [&](int w, int wo, int h, int ho, int m, int sh, int sn) {
     if (!(w == 64 || w == 128 || (w == 256 && !half_tile && !small_tile))) genw = true;      // whole lines per tile, tiles start at x = 0
-    return w >= 1 && wo == w && ho == h && sh == w * p.Cin && (long long)m * p.Cin * 2 < 0x7fffffffLL;
+    return w >= 1 && wo == w && ho == h && sh == w * p.Cin && (long long)sn == (long long)h * sh && (long long)m * p.Cin * 2 < 0x7fffffffLL;
   };
   // round 5: convs with <= 128 output channels run a 256-pixel x 128-channel tile on 4 x 2 waves (64 x 64 per wave, as the
   // 128-pixel tile's waves): no MFMAs and no weight stages for channels that do not exist
@@ -487,12 +488,12 @@ int osd_conv_sp_launch(const ConvKParams& pin, hipStream_t stream, bool general_
   if (p.n_seg > 0) {
     p.tilesM = 0;
     for (int i = 0; i < p.n_seg; ++i) {
-      if (!ok(p.seg[i].W, p.seg[i].Wo, p.seg[i].H, p.seg[i].Ho, p.seg[i].M, p.seg[i].sH))
+      if (!ok(p.seg[i].W, p.seg[i].Wo, p.seg[i].H, p.seg[i].Ho, p.seg[i].M, p.seg[i].sH, p.seg[i].sN))
         return osd_fail(OSD_ERR_UNSUPPORTED, "conv(sp): segment %d (width %d) is not a dense map under 2 GiB", i, p.seg[i].W);
       p.seg[i].tile_begin = p.tilesM;
       p.tilesM += cdiv(p.seg[i].M, BMx);
     }
-  } else if (!ok(p.W, p.Wo, p.H, p.Ho, p.M, p.sH)) {
+  } else if (!ok(p.W, p.Wo, p.H, p.Ho, p.M, p.sH, p.sN)) {
     return osd_fail(OSD_ERR_UNSUPPORTED, "conv(sp): not a dense map under 2 GiB (width %d)", p.W);
   }
   p.tilesN = cdiv(p.Cout, BNx);

@@ -200,13 +200,14 @@ int osd_conv_pred_launch(const ConvKParams& pin, hipStream_t stream) {
     for (int i = 0; i < p.n_seg; ++i) {
       ConvSeg& g = p.seg[i];
       if (g.mask != nullptr || g.res != nullptr) return osd_fail(OSD_ERR_UNSUPPORTED, "conv(pred): no residual / mask (segment %d)", i);
-      if (g.Ho != g.H || g.Wo != g.W || g.sH != g.W * p.Cin || (long long)g.M * p.Cin >= 0x7fffffffLL)
+      if (g.Ho != g.H || g.Wo != g.W || g.sH != g.W * p.Cin || (long long)g.sN != (long long)g.H * g.sH || (long long)g.M * p.Cin >= 0x7fffffffLL)
         return osd_fail(OSD_ERR_UNSUPPORTED, "conv(pred): segment %d is not a dense map under 2^31 elements", i);
       g.tile_begin = (int)tiles;
       tiles += (long long)(g.M / (g.H * g.W)) * cdiv(g.H, PT_R) * cdiv(g.W, PT_C);
     }
   } else {
-    if (p.Ho != p.H || p.Wo != p.W || p.sH != p.W * p.Cin || (long long)p.M * p.Cin >= 0x7fffffffLL)
+    // dense: the images follow each other without gaps (a patch's pixels are addressed from the image's first pixel at img * H * W * Cin)
+    if (p.Ho != p.H || p.Wo != p.W || p.sH != p.W * p.Cin || (long long)p.sN != (long long)p.H * p.sH || (long long)p.M * p.Cin >= 0x7fffffffLL)
       return osd_fail(OSD_ERR_UNSUPPORTED, "conv(pred): not a dense map under 2^31 elements");
     tiles = (long long)(p.M / (p.H * p.W)) * cdiv(p.H, PT_R) * cdiv(p.W, PT_C);
   }

@@ -888,6 +888,12 @@ __global__ void __launch_bounds__(256) bias_grad_kernel(const T* __restrict__ dy
 
 extern "C" int osd_bias_grad(const void* dy, float* db, int m, int c, int stride, int dtype, void* stream);
 
+// Every weight-gradient kernel addresses pixel m of a segment at m * cin (images one after the other, no gaps): the input
+// strides of the descriptor must say exactly that
+static bool wgrad_dense_input(const osd_conv_desc* d) {
+  return d->in_stride_w == d->cin && d->in_stride_h == d->w * d->cin && (long long)d->in_stride_n == (long long)d->h * d->w * d->cin;
+}
+
 struct WgradProblem {      // host-side description of one segment
   const osd_conv_desc* d;    // geometry: n, h, w, cin, cout, r, s, strides, pads, out_stride
   int n, h, w;
@@ -905,10 +911,12 @@ static int wgrad_xr_launch(int n_seg, const WgradProblem* pr, hipStream_t s) {
   const int bkp = x == 1 ? 64 : 32;
   WgradParams p;
   p.n_seg = n_seg;
+  p.sk_units = 0;               // no team mode
   long long work = 0;
   for (int i = 0; i < n_seg; ++i) {
     const osd_conv_desc* d = pr[i].d;
     WgradSeg& g = p.seg[i];
+    g.owner = 0;                // no owner mode: the filter-row kernel adds its tiles with atomics
     const int h = pr[i].h, w = pr[i].w;
     if (d->dtype != OSD_BF16 || d->r != 3 || d->s != 3 || d->stride_h != 1 || d->stride_w != 1 || d->pad_h != 1 || d->pad_w != 1 ||
         d->cout % 128 || d->cin % 128 || d->out_stride % 8 || !(w % bkp == 0 || bkp % w == 0))
@@ -936,15 +944,6 @@ static int wgrad_xr_launch(int n_seg, const WgradProblem* pr, hipStream_t s) {
     g.block_begin = (int)nblocks;
     nblocks += (long long)g.tilesCo * g.tilesCi * 3 * splits;
     if (nblocks > 0x7fffffffLL) return osd_fail(OSD_ERR_INVALID_ARG, "wgrad: bad grid");
-  }
-  // owner mode needs the segment's dW (and db: its adds stay atomic) to be named by no other segment of the launch; never in
-  // ordered mode (the partial tiles go to the scratch slots) or team mode (several teams add into one dW).  OSD_WGRAD_NO_OWNER=1: A/B
-  static int no_owner = -1;
-  if (no_owner < 0) { const char* e = getenv("OSD_WGRAD_NO_OWNER"); no_owner = (e && atoi(e) != 0) ? 1 : 0; }
-  for (int i = 0; i < n_seg; ++i) {
-    if (no_owner || d0->ordered_ws != nullptr || p.sk_units > 0) p.seg[i].owner = 0;
-    for (int j = 0; j < n_seg && p.seg[i].owner; ++j)
-      if (j != i && p.seg[j].dw == p.seg[i].dw) p.seg[i].owner = 0;
   }
   for (int i = n_seg; i < kMaxSeg; ++i) p.seg[i] = p.seg[0];
   p.n_blocks = (int)nblocks;
@@ -1167,8 +1166,7 @@ extern "C" int osd_conv2d_wgrad(const osd_conv_desc* d, const void* x, const voi
   const int epc = d->dtype == OSD_BF16 ? 8 : 4;
   const long long M = (long long)d->n * d->ho * d->wo;
   if (M <= 0 || M > 0x7fffffffLL) return osd_fail(OSD_ERR_INVALID_ARG, "wgrad: bad M");
-  if (d->in_stride_w != d->cin || d->in_stride_h != d->w * d->cin)
-    return osd_fail(OSD_ERR_UNSUPPORTED, "wgrad: dense NHWC input required");
+  if (!wgrad_dense_input(d)) return osd_fail(OSD_ERR_UNSUPPORTED, "wgrad: dense NHWC input required");
   hipStream_t s = OSD_STREAM(stream);
   if (d->cout <= 8 && (d->out_stride % epc != 0 || d->cin % epc != 0)) {   // prediction convs whose dy is not padded
     if (d->r * d->s > 9) return osd_fail(OSD_ERR_UNSUPPORTED, "wgrad: skinny kernel supports up to 9 taps");
@@ -1455,8 +1453,7 @@ extern "C" int osd_conv2d_wgrad_batched(const osd_conv_desc* d, int n_seg, const
   if (!d || !xs || !dys || !dws || n_seg < 1 || n_seg > kMaxSeg)
     return osd_fail(OSD_ERR_INVALID_ARG, "wgrad_batched: bad arguments");
   if (d->dtype != OSD_F32 && d->dtype != OSD_BF16) return osd_fail(OSD_ERR_INVALID_ARG, "wgrad: bad dtype");
-  if (d->in_stride_w != d->cin || d->in_stride_h != d->w * d->cin)
-    return osd_fail(OSD_ERR_UNSUPPORTED, "wgrad_batched: dense NHWC input required");
+  if (!wgrad_dense_input(d)) return osd_fail(OSD_ERR_UNSUPPORTED, "wgrad_batched: dense NHWC input required");
   WgradProblem pr[kMaxSeg];
   for (int i = 0; i < n_seg; ++i)
     pr[i] = WgradProblem{d, d->n, d->h, d->w, xs[i], dys[i], scales ? scales[i] : nullptr, dws[i], dbs ? dbs[i] : nullptr};
@@ -1488,8 +1485,7 @@ extern "C" int osd_conv2d_wgrad_mixed(int n_seg, const osd_conv_desc* descs, con
   WgradProblem pr[kMaxSeg];
   for (int i = 0; i < n_seg; ++i) {
     const osd_conv_desc* d = descs + i;
-    if (d->in_stride_w != d->cin || d->in_stride_h != d->w * d->cin)
-      return osd_fail(OSD_ERR_UNSUPPORTED, "wgrad_mixed: dense NHWC input required (segment %d)", i);
+    if (!wgrad_dense_input(d)) return osd_fail(OSD_ERR_UNSUPPORTED, "wgrad_mixed: dense NHWC input required (segment %d)", i);
     pr[i] = WgradProblem{d, d->n, d->h, d->w, xs[i], dys[i], scales ? scales[i] : nullptr, dws[i], dbs ? dbs[i] : nullptr};
   }
   return wgrad_launch(n_seg, pr, OSD_STREAM(stream));

@@ -190,7 +190,7 @@ def conv2d(x, pc, stride=1, pad=0, act=ACT_NONE, res=None, res_mode=RES_NONE, re
         _lib.call("osd_conv2d_fwd", C.byref(d), *args)
     _rec("conv", x=x, w=pc.w, bias=pc.bias, cout=pc.cout_store, r=pc.r, s=pc.s, stem=pc.stem, stride=stride, pad=pad, act=act,
          res=res, res_mode=res_mode, relu_in=bool(relu_in), act_scale=float(act_scale), act_scale_dev=act_scale_dev, mask=mask,
-         out=out)
+         out=out, algo=d.algo, key=key)
     return out
 
 
@@ -267,6 +267,7 @@ def _conv2d_two_sources(x, x2, x2_stride, pc, act, out, algo, pc2=None, bias=Non
     src2 = ConvSrc2(x2.contiguous().data_ptr(), pc2.w.data_ptr() if pc2 is not None else None, c2, x2.shape[1], x2.shape[2],
                     int(x2_stride))
     args = (_p(x), _p(pc.w), _p(bias), None, None, None, C.byref(src2), _p(out), _stream())
+    key = None
     if algo is None:
         key = ("src2", d.dtype, n, h, w, d.cout, c, c2, int(x2_stride), act, pc2 is not None)
         algo = ALGO_CACHE.get(key)
@@ -280,7 +281,7 @@ def _conv2d_two_sources(x, x2, x2_stride, pc, act, out, algo, pc2=None, bias=Non
     _lib.call("osd_conv2d_fwd", C.byref(d), *args)
     _rec("conv", x=x, x2=x2, x2_stride=int(x2_stride), w=pc.w, w2=None if pc2 is None else pc2.w, bias=bias, cout=pc.cout_store,
          r=1, s=1, stem=False, stride=1, pad=0, act=act, res=None, res_mode=RES_NONE, relu_in=False, act_scale=1.0,
-         act_scale_dev=None, mask=None, out=out)
+         act_scale_dev=None, mask=None, out=out, algo=d.algo, key=key)
     return out
 
 
@@ -415,8 +416,9 @@ def conv2d_multi(xs, pcs, stride=1, pad=0, act=ACT_NONE, residuals=None, res_mod
         for i in range(k):
             _rec("conv", x=xs[i], w=pcs[i].w, bias=pcs[i].bias, cout=pc.cout_store, r=pc.r, s=pc.s, stem=False, stride=stride, pad=pad,
                  act=act, res=None, res_mode=res_mode, relu_in=False, act_scale=float(act_scale), act_scale_dev=None, mask=None,
-                 out=outs[i])
+                 out=outs[i], algo=d.algo, key=None)
         return outs
+    key = None
     if algo is None:
         key = ("grouped", d.dtype, tuple(tuple(o.shape[:3]) for o in outs), d.cout, d.cin, d.r, d.s, stride, pad, d.res_mode,
                act, masks is not None)
@@ -429,7 +431,7 @@ def conv2d_multi(xs, pcs, stride=1, pad=0, act=ACT_NONE, residuals=None, res_mod
         _rec("conv", x=xs[i], w=pcs[i].w, bias=pcs[i].bias, cout=pc.cout_store, r=pc.r, s=pc.s, stem=False, stride=stride, pad=pad,
              act=act, res=None if residuals is None else residuals[i], res_mode=res_mode, relu_in=False,
              act_scale=float(act_scale), act_scale_dev=None if act_scale_devs is None else act_scale_devs[i],
-             mask=None if masks is None else masks[i], out=outs[i])
+             mask=None if masks is None else masks[i], out=outs[i], algo=d.algo, key=key)
     return outs
 
 
@@ -794,7 +796,7 @@ def conv2d_wgrad(x, dy, dw_packed, r, s, stride, pad, cout, scale=None, db=None,
         algo = _tune_wgrad(key, d, launch, dw_packed, db, [x.shape[2]]) if _TUNING[0] else 0
     d.algo = algo
     launch(dw_packed, db)
-    _rec("wgrad", items=[dict(x=x, dy=dy, dw=dw_packed, scale=scale, db=db, r=r, s=s, stride=stride, pad=pad, cout=cout)])
+    _rec("wgrad", items=[dict(x=x, dy=dy, dw=dw_packed, scale=scale, db=db, r=r, s=s, stride=stride, pad=pad, cout=cout)], algo=algo, key=key)
 
 
 PRED_G = 64      # columns of the prediction convs' gathered dy matrix (osd_pred_dy_gather)
@@ -854,7 +856,7 @@ def conv2d_wgrad_grouped(pairs, dw_packed, r, s, stride, pad, cout, scale=None, 
             wsp = torch.empty((need // 4 + 1,), device=x0.device, dtype=torch.float32)
             _lib.call("osd_conv2d_wgrad_pred", C.byref(d), k, xs, dys, ns, hs, ws, _p(dw_packed), _p(db), _p(wsp), st)
         _rec("wgrad", items=[dict(x=x, dy=dy, dw=dw_packed, scale=None, db=db, r=r, s=s, stride=stride, pad=pad, cout=cout)
-                             for x, dy in pairs])
+                             for x, dy in pairs], algo="pred", key=None)
         return
 
     def launch(dw, dbias):
@@ -867,7 +869,7 @@ def conv2d_wgrad_grouped(pairs, dw_packed, r, s, stride, pad, cout, scale=None, 
     d.algo = algo
     launch(dw_packed, db)
     _rec("wgrad", items=[dict(x=x, dy=dy, dw=dw_packed, scale=scale, db=db, r=r, s=s, stride=stride, pad=pad, cout=cout)
-                         for x, dy in pairs])
+                         for x, dy in pairs], algo=algo, key=key)
 
 
 def conv2d_wgrad_batched(items, r, s, stride, pad, cout, algo=None):
@@ -900,7 +902,7 @@ def conv2d_wgrad_batched(items, r, s, stride, pad, cout, algo=None):
     d.algo = algo
     launch([it[2] for it in items], [it[4] for it in items])
     _rec("wgrad", items=[dict(x=it[0], dy=it[1], dw=it[2], scale=it[3], db=it[4], r=r, s=s, stride=stride, pad=pad, cout=cout)
-                         for it in items])
+                         for it in items], algo=algo, key=key)
 
 
 def conv2d_wgrad_multi(items, r, s, stride, pad, cout, algo=None):
@@ -937,7 +939,7 @@ def conv2d_wgrad_multi(items, r, s, stride, pad, cout, algo=None):
     d.algo = algo
     launch(real_dws, real_dbs)
     _rec("wgrad", items=[dict(x=it[0], dy=it[1], dw=it[2], scale=it[3], db=it[4], r=r, s=s, stride=stride, pad=pad, cout=cout)
-                         for it in items])
+                         for it in items], algo=algo, key=key)
 
 
 def conv2d_wgrad_mixed(items, algo=None):
@@ -986,7 +988,7 @@ def conv2d_wgrad_mixed(items, algo=None):
     descs[0].algo = algo
     launch(real_dws, real_dbs)
     _rec("wgrad", items=[dict(x=it[0], dy=it[1], dw=it[2], scale=it[3], db=it[4], r=it[5], s=it[6], stride=it[7], pad=it[8],
-                              cout=it[9]) for it in items])
+                              cout=it[9]) for it in items], algo=algo, key=key)
 
 
 def bias_grad(dy, db, c):

@@ -5,13 +5,17 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import conv_ref as cr
 import golden_utils as gu
 from oracle import hotpath_ref as orc
+from oracle import launch_replay as lr
 
 pytestmark = pytest.mark.gpu
 
 DT = {"f32": torch.float32, "bf16": torch.bfloat16}
-# fp32 path: exact-fp32 MFMA, only summation order differs from oneDNN.  bf16: 8-bit mantissa inputs, fp32 accumulate.
+# fp32 path: exact-fp32 MFMA, only summation order differs from oneDNN.  bf16 results of bf16 operands are held to
+# tests/conv_ref.py's bound instead (one bf16 ulp of the float64 reference of the launch's own operands, `exact` below);
+# TOL["bf16"] is left for results that are not one rounding of such a launch.
 TOL = {"f32": dict(rtol=2e-5, atol=2e-5), "bf16": dict(rtol=3e-2, atol=3e-2)}
 
 
@@ -31,6 +35,20 @@ def to_nhwc(x, dtype):
 
 def from_nhwc(y):
     return y.float().cpu().permute(0, 3, 1, 2)
+
+
+def exact(x, pc, **kw):
+    """float64 reference of one conv launch from the kernel's OWN operands: x the device input (NHWC), pc the packed weights
+    (FrozenBN folded and rounded by the packer: oracle.launch_replay.unpack_weight) and its fp32 bias; kw as cr.conv_fwd.
+    -> NHWC float64 [n, ho, wo, cout_store] on x's device."""
+    return cr.conv_fwd(x, lr.unpack_weight(pc.w, pc.cout_store), pc.bias, **kw)
+
+
+def assert_bf16(y, ref, cout=None, what=""):
+    """y: what a bf16 kernel stored (NHWC); ref: the float64 result of its operands (`exact`).  The conv_ref bound: within one bf16
+    ulp of the rounded reference (+ 1e-5 x absmax), at most 2 % of the elements on the neighbouring value."""
+    c = ref.shape[-1] if cout is None else cout
+    return cr.assert_output(y[..., :c], ref[..., :c], what=what)
 
 
 CONV_CASES = [
@@ -54,9 +72,13 @@ def test_conv2d_bias_matches_torch(case, dt):
         x, wt = x.bfloat16().float(), wt.bfloat16().float()
     ref = F.conv2d(x, wt, b, stride=s, padding=p)
     pc = ops().pack_conv(wt.cuda(), bias=b.cuda(), dtype=DT[dt])
-    y = ops().conv2d(to_nhwc(x, DT[dt]), pc, stride=s, pad=p)
+    xx = to_nhwc(x, DT[dt])
+    y = ops().conv2d(xx, pc, stride=s, pad=p)
     assert y.shape[-1] == (cout + 3) // 4 * 4
-    torch.testing.assert_close(from_nhwc(y)[:, :cout], ref, **TOL[dt])
+    if dt == "bf16":
+        assert_bf16(y, exact(xx, pc, stride=s, pad=p), cout)
+    else:
+        torch.testing.assert_close(from_nhwc(y)[:, :cout], ref, **TOL[dt])
 
 
 @pytest.mark.parametrize("dt", ["f32", "bf16"])
@@ -70,8 +92,12 @@ def test_conv2d_frozenbn_residual_relu(dt):
     sd = {"bn.weight": bn[0], "bn.bias": bn[1], "bn.running_mean": bn[2], "bn.running_var": bn[3]}
     ref = F.relu(orc.frozen_bn(F.conv2d(x, wt), sd, "bn") + idn)
     pc = ops().pack_conv(wt.cuda(), bn=[t.cuda() for t in bn], dtype=DT[dt])
-    y = ops().conv2d(to_nhwc(x, DT[dt]), pc, act=ops().ACT_RELU, res=to_nhwc(idn, DT[dt]), res_mode=ops().RES_SAME)
-    torch.testing.assert_close(from_nhwc(y), ref, **TOL[dt])
+    xx, rr = to_nhwc(x, DT[dt]), to_nhwc(idn, DT[dt])
+    y = ops().conv2d(xx, pc, act=ops().ACT_RELU, res=rr, res_mode=ops().RES_SAME)
+    if dt == "bf16":          # the packed weights carry the FrozenBN fold and the rounding: the reference takes them from there
+        assert_bf16(y, exact(xx, pc, act=cr.ACT_RELU, res=rr, res_mode=cr.RES_SAME))
+    else:
+        torch.testing.assert_close(from_nhwc(y), ref, **TOL[dt])
 
 
 @pytest.mark.parametrize("dt", ["f32", "bf16"])
@@ -97,25 +123,35 @@ def test_conv2d_two_sources_is_conv3_plus_downsample(stride, dt):
         wcat = torch.cat([w3 * s3.view(-1, 1, 1, 1), wd * sdn.view(-1, 1, 1, 1)], 1)
         bias = (bn3[1] - bn3[2] * s3) + (bnd[1] - bnd[2] * sdn)
         pc = o.pack_conv(wcat.cuda(), bias=bias.cuda(), dtype=DT[dt])
-        tol = TOL[dt] if dt == "f32" else dict(rtol=3e-2, atol=3e-2)
+        tt, xx = to_nhwc(t2, DT[dt]), to_nhwc(x, DT[dt])
+        wp = lr.unpack_weight(pc.w, pc.cout_store)
+        ex = cr.conv_fwd(tt, wp[:, :cm], pc.bias, x2=xx, w2=wp[:, cm:cm + cx], x2_stride=stride, act=cr.ACT_RELU)
         done = 0
         for algo in [None] + [1 + v * 8 + t for v in (0, 1, 2, 3) for t in (0, 2, 7)]:
             try:
-                y = o.conv2d(to_nhwc(t2, DT[dt]), pc, act=o.ACT_RELU, x2=to_nhwc(x, DT[dt]), x2_stride=stride, algo=algo)
+                y = o.conv2d(tt, pc, act=o.ACT_RELU, x2=xx, x2_stride=stride, algo=algo)
             except Exception as e:      # noqa: BLE001  (a tile that does not fit LDS with this ring)
                 assert "does not fit" in str(e), (algo, e)
                 continue
-            torch.testing.assert_close(from_nhwc(y), ref, **tol)
+            if dt == "bf16":
+                assert_bf16(y, ex, what=algo)
+            else:
+                torch.testing.assert_close(from_nhwc(y), ref, **TOL[dt])
             done += 1
         assert done >= 8
         # the same with two separately packed convs (their own FrozenBN folds) and the summed bias: what the training
         # engine uses for the trainable stages, whose conv3 / downsample weights are repacked every step
         pa = o.pack_conv(w3.cuda(), bn=[t.cuda() for t in bn3], dtype=DT[dt])
         pb = o.pack_conv(wd.cuda(), bn=[t.cuda() for t in bnd], dtype=DT[dt])
+        bsum = pa.bias + pb.bias
+        ex = cr.conv_fwd(tt, lr.unpack_weight(pa.w, pa.cout_store), bsum, x2=xx, w2=lr.unpack_weight(pb.w, pb.cout_store),
+                         x2_stride=stride, act=cr.ACT_RELU)
         for algo in (None, 1 + 0, 1 + 3 * 8 + 2, 1 + 2 * 8 + 7):
-            y = o.conv2d(to_nhwc(t2, DT[dt]), pa, act=o.ACT_RELU, x2=to_nhwc(x, DT[dt]), x2_stride=stride, pc2=pb,
-                         bias=(pa.bias + pb.bias), algo=algo)
-            torch.testing.assert_close(from_nhwc(y), ref, **tol)
+            y = o.conv2d(tt, pa, act=o.ACT_RELU, x2=xx, x2_stride=stride, pc2=pb, bias=bsum, algo=algo)
+            if dt == "bf16":
+                assert_bf16(y, ex, what=algo)
+            else:
+                torch.testing.assert_close(from_nhwc(y), ref, **TOL[dt])
     with pytest.raises(Exception):       # 3x3 convs have no second source
         o.conv2d(to_nhwc(t2, DT[dt]), o.pack_conv(rnd(cout, cm + cx, 1, 1, seed=3).cuda(), bias=bias.cuda(), dtype=DT[dt]),
                  x2=to_nhwc(x[:, :, :2, :2], DT[dt]), x2_stride=stride)
@@ -130,8 +166,12 @@ def test_conv2d_fpn_lateral_upsample_add(dt):
         x, wt, top = x.bfloat16().float(), wt.bfloat16().float(), top.bfloat16().float()
     ref = F.conv2d(x, wt, b) + F.interpolate(top, scale_factor=2, mode="nearest")
     pc = ops().pack_conv(wt.cuda(), bias=b.cuda(), dtype=DT[dt])
-    y = ops().conv2d(to_nhwc(x, DT[dt]), pc, res=to_nhwc(top, DT[dt]), res_mode=ops().RES_UP2X)
-    torch.testing.assert_close(from_nhwc(y), ref, **TOL[dt])
+    xx, tp = to_nhwc(x, DT[dt]), to_nhwc(top, DT[dt])
+    y = ops().conv2d(xx, pc, res=tp, res_mode=ops().RES_UP2X)
+    if dt == "bf16":
+        assert_bf16(y, exact(xx, pc, res=tp, res_mode=cr.RES_UP2X))
+    else:
+        torch.testing.assert_close(from_nhwc(y), ref, **TOL[dt])
 
 
 @pytest.mark.parametrize("dt", ["f32", "bf16"])
@@ -151,6 +191,7 @@ def test_conv2d_identity_on_every_other_pixel(dt):
         ref = F.relu(F.conv2d(x, wt, b) + idn[:, :, ::2, ::2])
         pc = o.pack_conv(wt.cuda(), bias=b.cuda(), dtype=T)
         xx, rr = to_nhwc(x, T), to_nhwc(idn, T)
+        ex = exact(xx, pc, act=cr.ACT_RELU, res=rr, res_mode=cr.RES_DOWN2X)
         ran = 0
         for algo in [None] + o.conv_algo_candidates(cout, False):
             try:
@@ -158,7 +199,10 @@ def test_conv2d_identity_on_every_other_pixel(dt):
             except _lib.OsdError:
                 continue
             ran += 1
-            torch.testing.assert_close(from_nhwc(y), ref, **TOL[dt])
+            if dt == "bf16":
+                assert_bf16(y, ex, what=(n, hh, ww, algo))
+            else:
+                torch.testing.assert_close(from_nhwc(y), ref, **TOL[dt])
         assert ran >= 4
     with pytest.raises(Exception):       # an identity map that does not cover the output
         o.conv2d(xx, pc, act=o.ACT_RELU, res=to_nhwc(rnd(3, 128, 4, 4, seed=5), T), res_mode=o.RES_DOWN2X)
@@ -180,10 +224,17 @@ def test_conv2d_relu_in_and_exp_scale(dt):
     if dt == "bf16":
         x, wt = x.bfloat16().float(), wt.bfloat16().float()
     pc = ops().pack_conv(wt.cuda(), bias=b.cuda(), dtype=DT[dt])
-    y = ops().conv2d(to_nhwc(x, DT[dt]), pc, stride=2, pad=1, relu_in=True)          # P7 = conv(relu(P6)) fpn.py:98
-    torch.testing.assert_close(from_nhwc(y), F.conv2d(F.relu(x), wt, b, stride=2, padding=1), **TOL[dt])
-    y = ops().conv2d(to_nhwc(x, DT[dt]), pc, pad=1, act=ops().ACT_EXP_SCALE, act_scale=0.7)  # fcos.py:95-97
-    torch.testing.assert_close(from_nhwc(y), torch.exp(0.7 * F.conv2d(x, wt, b, padding=1)), **TOL[dt])
+    xx = to_nhwc(x, DT[dt])
+    y = ops().conv2d(xx, pc, stride=2, pad=1, relu_in=True)          # P7 = conv(relu(P6)) fpn.py:98
+    if dt == "bf16":
+        assert_bf16(y, exact(xx, pc, stride=2, pad=1, relu_in=True), 4)
+    else:
+        torch.testing.assert_close(from_nhwc(y), F.conv2d(F.relu(x), wt, b, stride=2, padding=1), **TOL[dt])
+    y = ops().conv2d(xx, pc, pad=1, act=ops().ACT_EXP_SCALE, act_scale=0.7)  # fcos.py:95-97
+    if dt == "bf16":
+        assert_bf16(y, exact(xx, pc, pad=1, act=cr.ACT_EXP_SCALE, act_scale=0.7), 4)
+    else:
+        torch.testing.assert_close(from_nhwc(y), torch.exp(0.7 * F.conv2d(x, wt, b, padding=1)), **TOL[dt])
 
 
 @pytest.mark.parametrize("dt", ["f32", "bf16"])
@@ -348,6 +399,7 @@ def test_conv2d_every_algorithm_gives_the_same_answer(dt):
     ref = F.relu(F.conv2d(x, wt, b, padding=1) + idn)
     pc = ops().pack_conv(wt.cuda(), bias=b.cuda(), dtype=DT[dt])
     xx, rr = to_nhwc(x, DT[dt]), to_nhwc(idn, DT[dt])
+    ex = exact(xx, pc, pad=1, act=cr.ACT_RELU, res=rr, res_mode=cr.RES_SAME)
     ran = 0
     # + conv_sp's general-width form forced; pixels=874: the latency-sized launches' deep-ring tiles (algos 58 / 59, round 6; bf16)
     cands = ops().conv_algo_candidates(cout, False, pixels=n * h * w) + [1 + 16 + 6]
@@ -358,7 +410,10 @@ def test_conv2d_every_algorithm_gives_the_same_answer(dt):
         except _lib.OsdError:
             assert not (dt == "bf16" and algo in (57, 58, 59, 60))
             continue
-        torch.testing.assert_close(from_nhwc(y), ref, **TOL[dt], msg=lambda m: "algo %d: %s" % (algo, m))
+        if dt == "bf16":
+            assert_bf16(y, ex, what="algo %d" % algo)
+        else:
+            torch.testing.assert_close(from_nhwc(y), ref, **TOL[dt], msg=lambda m: "algo %d: %s" % (algo, m))
         ran += 1
     assert ran >= 10
 
@@ -393,7 +448,8 @@ def test_conv2d_pixel_stationary_pointwise_kernel_is_bit_identical(m_shape, cin,
             algo = (o.CONV_ALGO_PX, o.CONV_ALGO_PX_WIDE)[rep & 1]      # eight waves of 16 pixels / four waves of 32
             y = o.conv2d(xx, pc, algo=algo, out=torch.full_like(base, 7.0), **kw)      # every element is written
             assert torch.equal(y, base), (sorted(kw), rep, (y.float() - base.float()).abs().max().item())
-        torch.testing.assert_close(from_nhwc(y), ref, **TOL["bf16"])
+        ekw = {k: v for k, v in kw.items() if k != "res_mode"}
+        assert_bf16(y, exact(xx, pc, res_mode=kw.get("res_mode", cr.RES_NONE), **ekw), what=(m_shape, sorted(kw)))
     pc3 = o.pack_conv((rnd(cout, cin, 3, 3, seed=6) / 48).cuda(), bias=b.cuda(), dtype=torch.bfloat16)
     with pytest.raises(_lib.OsdError):
         o.conv2d(xx, pc3, pad=1, algo=o.CONV_ALGO_PX)
@@ -437,21 +493,30 @@ def test_prediction_conv_data_gradient_as_a_gemm_over_the_gathered_dy(dt, cout):
     o.conv2d_wgrad_grouped(list(zip(dev_xs, dev_dys)), dw, 3, 3, 1, 1, cout, db=db, g=g)
     q0 = 0
     ref_dw, ref_db = torch.zeros(cout, cin, 3, 3), torch.zeros(cout)
-    for (n, h, ww), d, x in zip(sizes, dys, xs):
+    ex_dw = torch.zeros(cout, 3, 3, cin, dtype=torch.float64, device="cuda")
+    for (n, h, ww), d, x, dd, xd in zip(sizes, dys, xs, dev_dys, dev_xs):
         xr = x.clone().requires_grad_(True)
         wr = w.clone().requires_grad_(True)
         br = torch.zeros(cout, requires_grad=True)
         F.conv2d(xr, wr, br, padding=1).backward(d[:, :cout])
         got = dx[q0:q0 + n * h * ww].view(n, h, ww, cin).permute(0, 3, 1, 2).float().cpu()
-        torch.testing.assert_close(got, xr.grad, **TOL[dt])
+        if dt == "f32":
+            torch.testing.assert_close(got, xr.grad, **TOL[dt])
         ref_dw += wr.grad
         ref_db += br.grad
+        ex_dw += cr.conv_wgrad(xd, dd, 3, 3, 1, 1, cout)[0]
         q0 += n * h * ww
-    scale = float(ref_dw.abs().max())
-    assert float((dw.permute(0, 3, 1, 2).cpu() - ref_dw).abs().max()) <= (2e-2 if dt == "bf16" else 1e-4) * scale
+    # the data gradient is ONE 1x1 conv over G (K = 64) with the packed wd (itself the exact restatement of the master: below):
+    # one rounding of its float64 result; the weight gradient an fp32 accumulation of the stored operands
+    assert torch.equal(wd.float().cpu(), lr.pred_dgrad_pack_launch(master.cpu(), cout, cin).to(DT[dt]).float())
+    if dt == "bf16":
+        assert_bf16(dx.view(1, 1, -1, cin), cr.conv_fwd(g.view(1, 1, g.shape[0], 64), lr.unpack_weight(wd, cin), None))
+        cr.assert_accumulated(dw, ex_dw, "prediction-conv dW")
+    else:
+        scale = float(ref_dw.abs().max())
+        assert float((dw.permute(0, 3, 1, 2).cpu() - ref_dw).abs().max()) <= 1e-4 * scale
     torch.testing.assert_close(db.cpu(), ref_db, rtol=1e-3, atol=1e-3 * float(ref_db.abs().max()))
     # the gathered matrix itself: every column of every pixel, exactly
-    from oracle import launch_replay as lr
     assert torch.equal(g.float().cpu(), lr.pred_gather_launch([t.cpu() for t in dev_dys]).to(DT[dt]).float())
 
 
@@ -485,8 +550,11 @@ def test_conv2d_grouped_equals_per_level_launches(dt):
         ran += 1
     assert ran >= 8
     ys = o.conv2d_grouped(xx, pc, pad=1, act=o.ACT_RELU)
-    for x, y in zip(xs, ys):
-        torch.testing.assert_close(from_nhwc(y), F.relu(F.conv2d(x, wt, b, padding=1)), **TOL[dt])
+    for x, xd, y in zip(xs, xx, ys):
+        if dt == "bf16":
+            assert_bf16(y, exact(xd, pc, pad=1, act=cr.ACT_RELU), what=tuple(x.shape))
+        else:
+            torch.testing.assert_close(from_nhwc(y), F.relu(F.conv2d(x, wt, b, padding=1)), **TOL[dt])
     # prediction conv: 4 outputs, per-level learnable Scale read from device memory (fcos.py:93-96)
     w4, b4 = rnd(4, cin, 3, 3, seed=5) / 48, rnd(4, seed=6) * 0.1
     if dt == "bf16":
@@ -495,8 +563,11 @@ def test_conv2d_grouped_equals_per_level_launches(dt):
     scales = torch.tensor([0.5, 1.0, 1.5, 0.25, 2.0], device="cuda")
     ys = o.conv2d_grouped(xx, p4, pad=1, act=o.ACT_EXP_SCALE, act_scale_devs=[scales[i:i + 1] for i in range(5)])
     for i, (x, y) in enumerate(zip(xs, ys)):
-        ref = torch.exp(F.conv2d(x, w4, b4, padding=1) * float(scales[i]))
-        torch.testing.assert_close(from_nhwc(y)[:, :4], ref, **TOL[dt])
+        if dt == "bf16":
+            assert_bf16(y, exact(xx[i], p4, pad=1, act=cr.ACT_EXP_SCALE, act_scale=float(scales[i])), 4, what=i)
+        else:
+            ref = torch.exp(F.conv2d(x, w4, b4, padding=1) * float(scales[i]))
+            torch.testing.assert_close(from_nhwc(y)[:, :4], ref, **TOL[dt])
 
 
 def test_conv2d_grouped_rejects_bad_arguments():
@@ -542,9 +613,9 @@ def test_conv2d_software_pipelined_row_reuse_kernel_matches_the_dma_kernel():
     n, h, w, cin, cout = 2, 20, 64, 64, 256
     xf, wf, bf = rnd(n, cin, h, w, seed=7), rnd(cout, cin, 3, 3, seed=8) / (cin * 9) ** 0.5, rnd(cout, seed=9)
     pc = o.pack_conv(wf.cuda(), bias=bf.cuda(), dtype=torch.bfloat16)
-    y = o.conv2d(to_nhwc(xf, torch.bfloat16), pc, pad=1, algo=SP)
-    ref = torch.nn.functional.conv2d(xf.bfloat16().float(), wf.bfloat16().float(), bf, padding=1)
-    np.testing.assert_allclose(y.float().cpu().permute(0, 3, 1, 2).numpy(), ref.numpy(), rtol=2e-2, atol=2e-2)
+    xd = to_nhwc(xf, torch.bfloat16)
+    y = o.conv2d(xd, pc, pad=1, algo=SP)
+    assert_bf16(y, exact(xd, pc, pad=1))
     # grouped launch over three levels
     xs = [to_nhwc(rnd(2, 256, 24, 128, seed=11), torch.bfloat16), to_nhwc(rnd(2, 256, 12, 64, seed=12), torch.bfloat16),
           to_nhwc(rnd(1, 256, 3, 64, seed=13), torch.bfloat16)]
@@ -588,9 +659,9 @@ def test_conv2d_software_pipelined_kernel_on_a_128_channel_tile():
     n, h, w, cin, cout = 2, 20, 64, 128, 128
     xf, wf, bf = rnd(n, cin, h, w, seed=7), rnd(cout, cin, 3, 3, seed=8) / (cin * 9) ** 0.5, rnd(cout, seed=9)
     pc = o.pack_conv(wf.cuda(), bias=bf.cuda(), dtype=torch.bfloat16)
-    y = o.conv2d(to_nhwc(xf, torch.bfloat16), pc, pad=1, algo=SP)
-    ref = torch.nn.functional.conv2d(xf.bfloat16().float(), wf.bfloat16().float(), bf, padding=1)
-    np.testing.assert_allclose(y.float().cpu().permute(0, 3, 1, 2).numpy(), ref.numpy(), rtol=2e-2, atol=2e-2)
+    xd = to_nhwc(xf, torch.bfloat16)
+    y = o.conv2d(xd, pc, pad=1, algo=SP)
+    assert_bf16(y, exact(xd, pc, pad=1))
     xs = [to_nhwc(rnd(2, 128, 24, 128, seed=11), torch.bfloat16), to_nhwc(rnd(2, 128, 12, 64, seed=12), torch.bfloat16),
           to_nhwc(rnd(1, 128, 5, 7, seed=13), torch.bfloat16)]
     for xa, ya in zip(xs, o.conv2d_grouped(xs, pc, pad=1, algo=SP, _whole=True)):
@@ -647,9 +718,9 @@ def test_conv2d_software_pipelined_kernel_on_any_width():
     n, h, w, cin, cout = 2, 11, 13, 64, 256
     xf, wf, bf = rnd(n, cin, h, w, seed=7), rnd(cout, cin, 3, 3, seed=8) / (cin * 9) ** 0.5, rnd(cout, seed=9)
     pc = o.pack_conv(wf.cuda(), bias=bf.cuda(), dtype=torch.bfloat16)
-    y = o.conv2d(to_nhwc(xf, torch.bfloat16), pc, pad=1, algo=SP)
-    ref = torch.nn.functional.conv2d(xf.bfloat16().float(), wf.bfloat16().float(), bf, padding=1)
-    np.testing.assert_allclose(y.float().cpu().permute(0, 3, 1, 2).numpy(), ref.numpy(), rtol=2e-2, atol=2e-2)
+    xd = to_nhwc(xf, torch.bfloat16)
+    y = o.conv2d(xd, pc, pad=1, algo=SP)
+    assert_bf16(y, exact(xd, pc, pad=1))
     # P3..P7 of a 2 x 640 x 832 batch in ONE launch
     xs = [to_nhwc(rnd(2, 256, hh, ww, seed=20 + i), torch.bfloat16) for i, (hh, ww) in enumerate([(80, 104), (40, 52), (20, 26), (10, 13), (5, 7)])]
     wt = rnd(256, 256, 3, 3, seed=13) / (256 * 9) ** 0.5
@@ -697,11 +768,10 @@ def test_conv_algorithm_cache_is_keyed_on_the_full_geometry():
     w = rnd(256, 256, 3, 3, seed=1, scale=0.05)
     pc = o.pack_conv(w.cuda(), bias=torch.zeros(256).cuda(), dtype=torch.bfloat16)
     for shape in ((2, 256, 16, 128), (2, 256, 128, 16)):
-        x = rnd(*shape, seed=2)
+        xd = to_nhwc(rnd(*shape, seed=2), torch.bfloat16)
         with o.tuning():
-            y = o.conv2d(to_nhwc(x, torch.bfloat16), pc, pad=1)
-        ref = F.conv2d(x.bfloat16().float(), w.bfloat16().float(), padding=1)
-        torch.testing.assert_close(y.float().permute(0, 3, 1, 2).cpu(), ref, rtol=2e-2, atol=2e-1)
+            y = o.conv2d(xd, pc, pad=1)
+        assert_bf16(y, exact(xd, pc, pad=1), what=shape)
     keys = [k for k in o.ALGO_CACHE if k[0] == o.OSD_BF16 and k[4:8] == (256, 256, 3, 3)]
     assert len({k[1:4] for k in keys}) >= 2
 
@@ -736,7 +806,10 @@ def test_conv2d_multi_own_weights_strides_and_topdown_add(dt):
     # against torch on one segment (weights are really per segment: segment 1 with segment 0's weights must differ)
     ref = F.conv2d(from_nhwc(xs[1]).to(T).float(), ws[1].cpu().to(T).float(), bs[1].cpu(), stride=2).relu()
     y1 = o.conv2d_multi(xs, pcs, stride=2, act=o.ACT_RELU, _whole=True)[1]
-    torch.testing.assert_close(from_nhwc(y1), ref, **TOL[dt])
+    if dt == "bf16":
+        assert_bf16(y1, exact(xs[1], pcs[1], stride=2, act=cr.ACT_RELU))
+    else:
+        torch.testing.assert_close(from_nhwc(y1), ref, **TOL[dt])
     assert not torch.equal(y1, o.conv2d(xs[1], pcs[0], stride=2, act=o.ACT_RELU))
 
 
@@ -810,14 +883,58 @@ def test_prediction_conv_patch_kernel_matches_the_tile_kernels():
         for ya, ra in zip(ys, rs):
             d = (ya.float() - ra.float()).abs()
             assert bool((d <= 2.0 ** -6 * ra.float().abs().clamp(min=1e-3)).all()), (cout, tuple(ya.shape), d.max().item())
-        # the fp32 reference
-        xf = rnd(2, 256, 23, 40, seed=31)
-        y = o.conv2d(to_nhwc(xf, torch.bfloat16), pc, pad=1, algo=PRED)
-        ref = F.conv2d(xf.bfloat16().float(), wt.bfloat16().float(), pc.bias[:cout].cpu(), padding=1)
-        np.testing.assert_allclose(y.float().cpu()[..., :cout].permute(0, 3, 1, 2).numpy(), ref.numpy(), rtol=2e-2, atol=2e-2)
+        # the float64 reference
+        xd = to_nhwc(rnd(2, 256, 23, 40, seed=31), torch.bfloat16)
+        y = o.conv2d(xd, pc, pad=1, algo=PRED)
+        assert_bf16(y, exact(xd, pc, pad=1), cout)
+        for x in xs:
+            assert_bf16(o.conv2d(x, pc, pad=1, algo=PRED), exact(x, pc, pad=1), cout, what=tuple(x.shape))
     # refused: wide convs, strides, 1x1
     wide = o.pack_conv((rnd(64, 256, 3, 3, seed=4) / 48).cuda(), bias=torch.zeros(64).cuda(), dtype=torch.bfloat16)
     with pytest.raises(_lib.OsdError):
         o.conv2d(xs[2], wide, pad=1, algo=PRED)
     with pytest.raises(_lib.OsdError):
         o.conv2d(xs[2], pc, pad=1, stride=2, algo=PRED)
+
+
+# (n, h, w): every pixel tile T in 256 / 128 / 64 / 32 sees an M tail of 1 and of T - 1 (M = 513, 767, 257, 383, 129, 191, 65, 95,
+# 33, 63) and, with n > 1, image boundaries inside a tile
+_M_TAIL_SHAPES = [(3, 9, 19), (1, 13, 59), (1, 1, 257), (1, 1, 383), (3, 1, 43), (1, 1, 191), (1, 5, 13), (5, 1, 19), (3, 1, 11), (1, 7, 9)]
+
+
+@pytest.mark.parametrize("case", [
+    # cin, cout, k, stride, shapes
+    (64, 256, 3, 1, _M_TAIL_SHAPES),
+    (192, 320, 3, 1, [(3, 9, 19), (1, 1, 257), (3, 1, 43)]),            # channel tails: K not a whole 128-channel slab, N not a whole tile
+    (64, 72, 1, 1, [(3, 9, 19), (1, 1, 383), (5, 1, 19)]),               # cout 72: 8 past a 64-channel tile
+    (64, 256, 3, 1, [(2, 5, w) for w in (1, 2, 3, 63, 65, 127, 129)]),   # conv_sp's general-width form on awkward widths
+    (128, 256, 3, 2, [(2, 13, 17), (1, 9, 31)]),                         # stride 2 on odd maps
+    (128, 128, 1, 2, [(2, 13, 17), (3, 7, 9)]),
+])
+def test_conv2d_every_algorithm_at_tile_edges_matches_the_float64_reference(case):
+    """Every algorithm the tuner may pick (and the library default), bf16, at the shapes where tiled kernels go wrong: M tails of 1 and
+    of tile - 1 pixels for each pixel tile, image boundaries inside a tile, channel tails that fill no tile, conv_sp's general width
+    on widths 1..129, stride 2 on odd maps — residual + ReLU epilogue, against the float64 reference of the launch's own operands
+    under the one-ulp bound (tests/conv_ref.py)."""
+    from oneshotdet_amd import _lib
+    o = ops()
+    cin, cout, k, st, shapes = case
+    p = k // 2
+    wt = rnd(cout, cin, k, k, seed=2) / (cin * k * k) ** 0.5
+    pc = o.pack_conv(wt.cuda(), bias=rnd(cout, seed=3).cuda(), dtype=torch.bfloat16)
+    ran = {}
+    for i, (n, h, w) in enumerate(shapes):
+        ho, wo = o.conv_out(h, k, st, p), o.conv_out(w, k, st, p)
+        xx = to_nhwc(rnd(n, cin, h, w, seed=10 + i), torch.bfloat16)
+        rr = to_nhwc(rnd(n, pc.cout_store, ho, wo, seed=20 + i), torch.bfloat16)
+        ex = exact(xx, pc, stride=st, pad=p, act=cr.ACT_RELU, res=rr, res_mode=cr.RES_SAME)
+        cands = [0] + o.conv_algo_candidates(pc.cout_store, False, pixels=n * ho * wo) + ([1 + 16 + 6] if k == 3 and st == 1 else [])
+        for algo in cands:
+            try:
+                y = o.conv2d(xx, pc, stride=st, pad=p, act=o.ACT_RELU, res=rr, res_mode=o.RES_SAME, algo=algo)
+            except _lib.OsdError as e:
+                assert getattr(e, "code", -2) == -2, (algo, e)
+                continue
+            assert_bf16(y, ex, what=((n, h, w), algo))
+            ran[algo] = ran.get(algo, 0) + 1
+    assert ran.get(0) == len(shapes) and len(ran) >= 6, ran

@@ -15,10 +15,13 @@ INPUT TENSORS (teacher forcing) in fp32 and rounded once.  Bars, per launch:
                  cosine >= 0.99999
 and the chain's coverage is asserted: every conv, GroupNorm, correlation, pooling, loss-gradient and weight-gradient launch
 of the step is replayed, and every trainable tensor's gradient is accounted for by the replayed launches."""
+import time
+
 import numpy as np
 import pytest
 import torch
 
+import conv_ref as cr
 import golden_utils as gu
 from oneshotdet_amd import spec, synth
 from oracle import launch_replay as lr
@@ -50,6 +53,7 @@ class Replayer(object):
         w["flips"] = max(w["flips"], res["flips"])
         if not res["ok"] or res["flips"] > self.flip_cap:
             self.failures.append((kind, what, tuple(got.shape), res))
+        return res
 
     def _accumulate(self, tensor, value):
         slot = self.acc.setdefault(tensor.data_ptr(), [tensor, torch.zeros(tensor.shape, dtype=torch.float32)])
@@ -260,3 +264,139 @@ def test_every_launch_at_the_benchmark_geometry_matches_its_cpu_restatement():
     print("\nconfig1 bf16: %d launches: %s\n  worst per kind: %s\n  worst accumulated-gradient error %.2e"
           % (len(trace), rp.counts, rp.worst, worst_acc))
     assert not rp.failures, rp.failures[:6]
+
+
+class Fp64Replayer(Replayer):
+    """The Replayer with every conv and weight-gradient launch recomputed in float64 ON THE GPU (tests/conv_ref.py: sums of shifted
+    matmuls) — the benchmark's batch of eight 800 x 1024 images costs seconds there instead of many minutes of CPU convolutions —
+    and each launch's (kind, algorithm) recorded: `by_algo` (kind, algo) -> [launches, worst error], `seen` the (tuner key, algo)
+    of every replayed conv / weight-gradient launch.  The other launch kinds keep the CPU restatement.  Accumulated gradients are
+    summed in float64 on the GPU."""
+
+    def __init__(self, flip_cap=0.02):
+        super().__init__(flip_cap)
+        self.by_algo = {}
+        self.seen = set()
+        self.writers = {}          # data_ptr of an accumulated gradient -> {(kind, algo) of the launches that added into it}
+
+    def _accumulate(self, tensor, value):
+        slot = self.acc.setdefault(tensor.data_ptr(), [tensor, torch.zeros(tensor.shape, dtype=torch.float64, device="cuda")])
+        slot[1] += value.to("cuda", torch.float64).reshape(tensor.shape)
+
+    def _note(self, kind, algo, err):
+        ent = self.by_algo.setdefault((kind, algo), [0, 0.0])
+        ent[0] += 1
+        ent[1] = max(ent[1], err)
+
+    def do_conv(self, r):
+        out = r["out"]
+        sc = float(r["act_scale_dev"].float().reshape(-1)[0]) if r["act_scale_dev"] is not None else r["act_scale"]
+        if r["stem"]:           # the packed NHWC4 image already carries the padding: 7 x 8 taps, stride 2, cropped to the output
+            ref = cr.conv_fwd(r["x"], lr.unpack_weight(r["w"], r["cout"], stem=True), r["bias"], stride=2, act=r["act"],
+                              out_hw=tuple(out.shape[1:3]))
+        else:
+            w = lr.unpack_weight(r["w"], r["cout"])
+            x2, w2 = r.get("x2"), None
+            if x2 is not None:
+                c1, c2 = r["x"].shape[-1], x2.shape[-1]
+                w2 = w[:, c1:c1 + c2] if r.get("w2") is None else lr.unpack_weight(r["w2"], r["cout"])[:, :c2]
+                w = w[:, :c1]
+            ref = cr.conv_fwd(r["x"], w, r["bias"], stride=r["stride"], pad=r["pad"], res=r["res"], res_mode=r["res_mode"],
+                              mask=r["mask"], act=r["act"], act_scale=sc, relu_in=r["relu_in"], x2=x2, w2=w2,
+                              x2_stride=r.get("x2_stride", 1))
+        kind = "conv%dx%d%s" % (r["r"], r["s"], "_src2" if r.get("x2") is not None else "")
+        res = self._check(kind, out, ref.float().cpu(), "algo %s stride %d act %d res %d mask %d" % (
+            r.get("algo"), r["stride"], r["act"], r["res_mode"], r["mask"] is not None))
+        self._note(kind, r.get("algo"), res["worst_ulp"] if out.dtype == torch.bfloat16 else res["worst_rel"])
+        self.seen.add((r.get("key"), r.get("algo")))
+
+    def do_wgrad(self, r):
+        self.counts["wgrad"] = self.counts.get("wgrad", 0) + 1
+        self._note("wgrad", r.get("algo"), 0.0)
+        self.seen.add((r.get("key"), r.get("algo")))
+        for it in r["items"]:
+            dw, db = cr.conv_wgrad(it["x"], it["dy"], it["r"], it["s"], it["stride"], it["pad"], it["cout"], scale=it["scale"],
+                                   want_bias=it["db"] is not None)
+            self._accumulate(it["dw"], dw)
+            self.writers.setdefault(it["dw"].data_ptr(), set()).add(("wgrad", r.get("algo")))
+            if it["db"] is not None:
+                self._accumulate(it["db"], db)
+                self.writers.setdefault(it["db"].data_ptr(), set()).add(("wgrad", r.get("algo")))
+
+    def check_accumulated(self, tol=cr.ACC_TOL):
+        """The accumulated-gradient bar of tests/conv_ref.py per tensor; each tensor's error is also charged to the weight-gradient
+        launches that wrote it (by_algo)."""
+        worst = 0.0
+        for ptr, (tensor, ref) in self.acc.items():
+            res = cr.check_accumulated(tensor.float(), ref, tol=tol)
+            worst = max(worst, res["err"])
+            for ka in self.writers.get(ptr, ()):
+                self.by_algo[ka][1] = max(self.by_algo[ka][1], res["err"])
+            if not res["ok"]:
+                self.failures.append(("accumulated gradient", tuple(ref.shape), res))
+        return worst
+
+
+def _bench_batch(dt):
+    """bench.py's default training batch: 8 distinct 800 x 1024 targets, their queries and box sets (rank 0's seeds)."""
+    from oneshotdet_amd import train
+    B = 8
+    images = torch.from_numpy(synth.make_images("bench.target", B, 800, 1024, seed=1000)).cuda()
+    queries = torch.from_numpy(synth.make_images("bench.query", B, 127, 127, seed=1000)).cuda()
+    gts = synth.make_gt_boxes(B, 800, 1024, seed=1000, max_boxes=6)
+    gtb = torch.zeros(B, 6, 4)
+    for i, g in enumerate(gts):
+        gtb[i, :len(g)] = torch.from_numpy(g)
+    cnt = torch.tensor([len(g) for g in gts], dtype=torch.int32)
+    eng = train.TrainEngine(synth.make_state_dict(spec.hot_path_shapes()), dtype=DT[dt])
+    return eng, images, queries, gtb.cuda(), cnt.cuda()
+
+
+def test_every_launch_of_the_tuned_batch8_benchmark_step_matches_its_restatement():
+    """bench.py's measured configuration: the bf16 training step at bs = 8 (800 x 1024) with the kernels `ops.tuning()` picks for
+    THESE shapes (the tuner's choices depend on the pixel count: deep-ring tiles, weight-gradient split targets, team / owner mode and
+    the grouped split points differ from bs = 1), the default schedule (streams, one-pass GroupNorm).  One tuned step, then a traced
+    step replayed launch by launch with the bars above — conv and weight-gradient launches against their float64 restatement on the
+    GPU.  Coverage: every tuner-cache key the step consulted was replayed with the algorithm cached for it, and every trainable
+    tensor's gradient is accounted for."""
+    from oneshotdet_amd import ops
+    t0 = time.time()
+    eng, img, q, gtb, cnt = _bench_batch("bf16")
+    with ops.tuning():
+        eng.forward_backward(img, q, gtb, cnt, with_proposals=False)
+    torch.cuda.synchronize()
+    t_tune = time.time() - t0
+    caches = {"ALGO_CACHE": ops.ALGO_CACHE, "WGRAD_ALGO_CACHE": ops.WGRAD_ALGO_CACHE, "SPLIT_CACHE": ops.SPLIT_CACHE}
+    for c in caches.values():
+        c.hits = {}
+        c.census = True
+    try:
+        _, trace = _traced(lambda: eng.forward_backward(img, q, gtb, cnt, with_proposals=False))
+    finally:
+        for c in caches.values():
+            c.census = False
+    t1 = time.time()
+    rp = Fp64Replayer()
+    rp.run(trace)
+    worst_acc = rp.check_accumulated()
+    table = "\n".join("  %-12s algo %-5s %4d launches  worst %s %.3g" % (k, a, n, "ulp" if k != "wgrad" else "acc", w)
+                      for (k, a), (n, w) in sorted(rp.by_algo.items(), key=lambda kv: (kv[0][0], str(kv[0][1]))))
+    print("\nbs=8 tuned bf16 step: tuning + step %.1f s, replay of %d launches %.1f s\n%s\n  other kinds: %s\n  worst accumulated-gradient "
+          "error %.2e of absmax over %d tensors" % (t_tune, len(trace), time.time() - t1, table,
+                                                   {k: {a: round(b, 4) for a, b in v.items()} for k, v in rp.worst.items() if not k.startswith("conv")},
+                                                   worst_acc, len(rp.acc)))
+    assert not rp.failures, rp.failures[:6]
+    # coverage: every key the traced step looked up was tuned, and a replayed launch ran the cached algorithm under it
+    for name, c in caches.items():
+        missing = [k for k in c.hits if k not in c]
+        assert not missing, (name, missing[:4])
+        if name != "SPLIT_CACHE":       # (a split point shows as the grouped launches it produced: their own keys above)
+            unseen = [k for k in c.hits if (k, c[k]) not in rp.seen]
+            assert not unseen, (name, unseen[:4])
+    assert ops.ALGO_CACHE.hits and ops.WGRAD_ALGO_CACHE.hits
+    for kind in ("conv1x1", "conv3x3", "conv7x1", "wgrad", "gn_relu", "gn_relu_bwd", "fcos_loss_grad"):
+        assert any(k == kind for k, _ in rp.by_algo) or rp.counts.get(kind, 0) > 0, "no %s launch in the trace" % kind
+    flat_lo, flat_hi = eng.flat_g.data_ptr(), eng.flat_g.data_ptr() + eng.flat_g.numel() * 4
+    covered = sum(ref.numel() for t, ref in rp.acc.values() if flat_lo <= t.data_ptr() < flat_hi)
+    total = sum(int(np.prod(s)) for n_, s in eng._plan if n_ != "rpn.head.scales")
+    assert covered == total, (covered, total)
