@@ -4,6 +4,9 @@ RyanXLi/OneshotDet drive it (both stages, SGD with the reference's parameter gro
     python examples/train.py [--iters 20] [--batch 2] [--dtype bf16|f32] [--first-stage-only] [--out /tmp/osd_run]
                              [--shared-backbone]        # one backbone for target and query (SIAMESE_BACKBONE False)
                              [--no-supp-roialign]       # the query pyramid pooled by global average (SUPP_ROIALIGN False)
+                             [--no-center-sample]       # positives inside the whole box (FCOS.CENTER_SAMPLE False)
+                             [--loc-loss-type giou|iou|linear_iou]      # the regression loss (FCOS.LOC_LOSS_TYPE)
+    python examples/train.py --no-center-sample --loc-loss-type iou ...    # the loss of the reference's defaults (defaults.py:309-311)
     python examples/train.py --shared-backbone --no-supp-roialign ...      # the 0930 model (configs/fcos/0930fixed_thres.yaml)
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 examples/train.py ...      # one rank per GPU
 
@@ -57,9 +60,13 @@ def main():
     ap.add_argument("--checkpoint-period", type=int, default=10)
     ap.add_argument("--shared-backbone", action="store_true", help="one backbone for target and query (SIAMESE_BACKBONE False)")
     ap.add_argument("--no-supp-roialign", action="store_true", help="pool the query pyramid by global average (SUPP_ROIALIGN False)")
+    ap.add_argument("--no-center-sample", action="store_true", help="positives inside the whole box (FCOS.CENTER_SAMPLE False)")
+    ap.add_argument("--loc-loss-type", default=spec.LOC_LOSS_TYPE, choices=list(spec.LOC_LOSS_TYPES),
+                    help="regression loss (FCOS.LOC_LOSS_TYPE): 1 - giou, -log(iou) or 1 - iou")
     args = ap.parse_args()
     siamese = not args.shared_backbone
     roialign = not args.no_supp_roialign
+    center_sample = not args.no_center_sample
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
     dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float32
@@ -67,12 +74,13 @@ def main():
 
     def make_engine(sd):
         return train.TrainEngine(sd, dtype=dtype, lr=0.0005, second_stage=not args.first_stage_only, siamese_backbone=siamese,
-                                 supp_roialign=roialign)
+                                 supp_roialign=roialign, center_sample=center_sample, loc_loss_type=args.loc_loss_type)
     start = 0
     last = os.path.join(args.out, "last_checkpoint")
     if args.resume and os.path.exists(last):
         eng, start = checkpoint.resume_training(open(last).read().strip(), make_engine, siamese_backbone=siamese,
-                                                supp_roialign=roialign)
+                                                supp_roialign=roialign, center_sample=center_sample,
+                                                loc_loss_type=args.loc_loss_type)
         print("resumed at iteration", start)
     else:
         eng = make_engine(synth.make_state_dict(shapes))      # or checkpoint.load_checkpoint / load_c2_resnet, see detect.py

@@ -548,6 +548,25 @@ int osd_fcos_loss_levels(int phase, int n_levels, const void* const* cls_ctrs, c
                          const int32_t* ws, const int32_t* strides, const float* size_lo, const float* size_hi, float radius,
                          float gamma, float alpha, const float* const* scale_devs, float* sums, void* const* d_cls_ctrs,
                          void* const* d_regs, int grad_stride, float* const* d_scale_raws, int dtype, void* stream);
+/* The reference's other loss modes.  center_sample (FCOS.CENTER_SAMPLE; modeling/rpn/fcos/loss.py:168-177): non-zero = a location
+ * is positive inside a box's sampling region of `radius` strides (with get_sample_region's quirk, loss.py:58-61: nothing is positive
+ * in an image whose FIRST box has centre x 0); 0 = inside the whole box, min(l, t, r, b) > 0, no region and no quirk (`radius` is not
+ * read).  loc_loss_type (FCOS.LOC_LOSS_TYPE; layers/iou_loss.py:34-41) with iou = (I + 1) / (U + 1): GIOU 1 - giou, IOU -log(iou),
+ * LINEAR_IOU 1 - iou; sums[3] is sum_w * that loss.  Any other value: OSD_ERR_INVALID_ARG, nothing is launched.  Everything else
+ * as osd_fcos_loss_level / osd_fcos_loss_levels, which are these with (1, OSD_LOC_LOSS_GIOU), the config of record. */
+#define OSD_LOC_LOSS_GIOU 0
+#define OSD_LOC_LOSS_IOU 1
+#define OSD_LOC_LOSS_LINEAR_IOU 2
+int osd_fcos_loss_level_opt(int phase, const void* cls_ctr, const void* reg, const float* gt_boxes, const int32_t* gt_count,
+                            int max_gt, int n, int h, int w, int stride, float size_lo, float size_hi, float radius,
+                            float gamma, float alpha, const float* scale_dev, float* sums, void* d_cls_ctr, void* d_reg,
+                            int grad_stride, float* d_scale_raw, int dtype, int center_sample, int loc_loss_type, void* stream);
+int osd_fcos_loss_levels_opt(int phase, int n_levels, const void* const* cls_ctrs, const void* const* regs,
+                             const float* gt_boxes, const int32_t* gt_count, int max_gt, int n, const int32_t* hs,
+                             const int32_t* ws, const int32_t* strides, const float* size_lo, const float* size_hi, float radius,
+                             float gamma, float alpha, const float* const* scale_devs, float* sums, void* const* d_cls_ctrs,
+                             void* const* d_regs, int grad_stride, float* const* d_scale_raws, int dtype, int center_sample,
+                             int loc_loss_type, void* stream);
 /* losses[4] = {loss_cls, loss_reg, loss_centerness, num_pos} */
 int osd_fcos_loss_finalize(const float* sums, float* losses, int n, void* stream);
 /* ... and, in the same launch, the gradient of the learnable per-level Scale (fcos.py:81, 95-97): d_scales[l] += d_scale_raw[l] /

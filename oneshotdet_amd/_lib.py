@@ -103,6 +103,8 @@ SIGNATURES = {
     "osd_grad_wire_cast": (_i, [_p, _p, _i64, _i, _p]),
     "osd_fcos_loss_level": (_i, [_i, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _p, _p, _p, _p, _i, _p, _i, _p]),
     "osd_fcos_loss_levels": (_i, [_i, _i, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _p, _f, _f, _f, _p, _p, _p, _p, _i, _p, _i, _p]),
+    "osd_fcos_loss_level_opt": (_i, [_i, _p, _p, _p, _p, _i, _i, _i, _i, _i, _f, _f, _f, _f, _f, _p, _p, _p, _p, _i, _p, _i, _i, _i, _p]),
+    "osd_fcos_loss_levels_opt": (_i, [_i, _i, _p, _p, _p, _p, _i, _i, _p, _p, _p, _p, _p, _f, _f, _f, _p, _p, _p, _p, _i, _p, _i, _i, _i, _p]),
     "osd_fcos_loss_finalize": (_i, [_p, _p, _i, _p]),
     "osd_fcos_loss_finalize_scales": (_i, [_p, _p, _i, _p, _p, _p, _i, _p]),
     "osd_roi_pool_levels": (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _i, _p]),

@@ -11,7 +11,8 @@ siamese_backbone (FEW_SHOT.SIAMESE_BACKBONE): True = the two-backbone model (a s
 `backbone.*` by that suffix match, as the reference does); False = the shared-backbone model, whose key set has no
 `supp_backbone.*` (a two-backbone file's query backbone is ignored, as the reference ignores keys its model does not have).
 supp_roialign (FEW_SHOT.SUPP_ROIALIGN) changes no key: the query pooling has no weights, so loading is the same in both modes;
-training checkpoints record it, and `resume_training` refuses to continue a run in the other mode.
+training checkpoints record it, and `resume_training` refuses to continue a run in the other mode.  The same holds for the loss
+options center_sample / loc_loss_type (FCOS.CENTER_SAMPLE / FCOS.LOC_LOSS_TYPE): the loss has no parameters.
 """
 import os
 import pickle
@@ -112,20 +113,35 @@ def save_training_checkpoint(path, engine, iteration, tag_last=True):
     """utils/checkpoint.py:33-50 as the trainer calls it (engine/trainer.py:111-119): model + optimizer + iteration.
     `optimizer` holds TrainEngine.optimizer_state_dict() (momentum buffers under reference names, steps taken, lr);
     `siamese_backbone` the engine's mode (a shared engine writes no `supp_backbone.*`); `supp_roialign` its query pooling (the
-    only record of it: the pooling has no weights)."""
+    only record of it: the pooling has no weights); `center_sample` / `loc_loss_type` the FCOS loss it trained with (likewise)."""
     return save_checkpoint(path, engine.state_dict(), tag_last=tag_last, optimizer=engine.optimizer_state_dict(),
                            iteration=int(iteration), siamese_backbone=bool(getattr(engine, "siamese_backbone", True)),
-                           supp_roialign=bool(getattr(engine, "supp_roialign", True)))
+                           supp_roialign=bool(getattr(engine, "supp_roialign", True)),
+                           center_sample=bool(getattr(engine, "center_sample", spec.CENTER_SAMPLE)),
+                           loc_loss_type=str(getattr(engine, "loc_loss_type", spec.LOC_LOSS_TYPE)))
 
 
-def resume_training(path, make_engine, siamese_backbone=None, supp_roialign=None):
+def _loss_name(mode):
+    return "the %s FCOS loss (center_sample=%r, loc_loss_type=%r)" % (
+        ("centre-sampled " if mode[0] else "whole-box ") + mode[1], mode[0], mode[1])
+
+
+def resume_training(path, make_engine, siamese_backbone=None, supp_roialign=None, center_sample=None, loc_loss_type=None):
     """Load a checkpoint written by save_training_checkpoint: make_engine(state_dict) -> TrainEngine; its momentum and
     step count are restored.  Returns (engine, iteration).  The file's mode (recorded by save_training_checkpoint; for
     older files: whether it holds `supp_backbone.*`) must be the engine's: a resumed run never ties or unties weights
     behind the caller's back.  siamese_backbone: the mode the caller expects (None: whatever the file holds).  The same
     for the query pooling: supp_roialign is the caller's expectation, the file's record (True when it has none, the
-    files written before the option existed) must match it and the engine's."""
+    files written before the option existed) must match it and the engine's.  And for the FCOS loss: center_sample /
+    loc_loss_type are the caller's expectations (None: whatever the file holds), a file without the fields was trained with
+    (True, "giou"), the only loss there was."""
     data = _read(path)
+    loss = (data.get("center_sample"), data.get("loc_loss_type"))
+    loss = (spec.CENTER_SAMPLE if loss[0] is None else bool(loss[0]), spec.LOC_LOSS_TYPE if loss[1] is None else str(loss[1]))
+    want = spec.loss_mode(loss[0] if center_sample is None else center_sample, loss[1] if loc_loss_type is None else loc_loss_type)
+    if want != loss:
+        raise ValueError("%s was trained with %s; resuming it with %s would continue the run on another objective: build the "
+                         "engine with center_sample=%r, loc_loss_type=%r" % (path, _loss_name(loss), _loss_name(want), loss[0], loss[1]))
     pool = data.get("supp_roialign")
     pool = True if pool is None else bool(pool)
     if supp_roialign is not None and bool(supp_roialign) != pool:
@@ -146,6 +162,9 @@ def resume_training(path, make_engine, siamese_backbone=None, supp_roialign=None
     if bool(getattr(eng, "supp_roialign", True)) != pool:
         raise ValueError("%s was trained with %s but make_engine built an engine with %s (supp_roialign=%r)"
                          % (path, _POOL[pool], _POOL[not pool], not pool))
+    built = (bool(getattr(eng, "center_sample", spec.CENTER_SAMPLE)), str(getattr(eng, "loc_loss_type", spec.LOC_LOSS_TYPE)))
+    if built != loss:
+        raise ValueError("%s was trained with %s but make_engine built an engine with %s" % (path, _loss_name(loss), _loss_name(built)))
     if "optimizer" in extras and isinstance(extras["optimizer"], dict) and "momentum_buffer" in extras["optimizer"]:
         eng.load_optimizer_state_dict(extras["optimizer"])
     return eng, int(extras.get("iteration", 0))

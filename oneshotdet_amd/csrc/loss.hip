@@ -2,8 +2,11 @@
 // (modeling/rpn/fcos/loss.py:52-204), sigmoid focal loss in the CUDA-kernel form
 // (csrc/cuda/SigmoidFocalLoss_cuda.cu:21-101), GIoU loss weighted by the centerness target
 // (layers/iou_loss.py:10-49, loss.py:263-267) and BCE-with-logits centerness loss (loss.py:268-271).
+// The reference's other modes are compile-time parameters of the same body: FCOS.CENTER_SAMPLE False (loss.py:176-177: inside the
+// WHOLE box, no sampling region) and FCOS.LOC_LOSS_TYPE 'iou' / 'linear_iou' (iou_loss.py:36-39); loc_loss below is 1 - giou,
+// -log(iou) or 1 - iou accordingly.
 // Two passes per FPN level over [N][H*W] locations (targets are recomputed, nothing per-location is stored):
-//   pass A accumulates  sums = {num_pos, sum_w, sum_focal, sum_w*(1-giou), sum_bce}
+//   pass A accumulates  sums = {num_pos, sum_w, sum_focal, sum_w*loc_loss, sum_bce}
 //   pass B writes the gradients w.r.t. (logit, centerness) and w.r.t. s = scale*bbox_pred (pre-exp), using
 //          cls = sum_focal/(num_pos+N), reg = sum_wg/sum_w, ctr = sum_bce/num_pos, total = cls + reg + ctr.
 #include "osd_common.h"
@@ -23,23 +26,31 @@ struct Target {
   float l, t, r, b;
 };
 
+// CS = FCOS.CENTER_SAMPLE.  true: a location is inside a box when it is inside the box's sampling region (get_sample_region,
+// loss.py:52-99); false: when it is inside the whole box (loss.py:176-177) — no region, so the quirk below does not exist there.
+template <bool CS>
 __device__ __forceinline__ Target assign_target(float x, float y, const float* __restrict__ gt, int ng, const LossLevel lv) {
   Target out;
   out.label = 0;
   out.l = out.t = out.r = out.b = 0.f;
   float best = kInf;
   // quirk of get_sample_region (loss.py:58-60): no sampling region at all when the first box's centre x is 0
-  const bool no_region = (ng == 0) || ((gt[0] + gt[2]) * 0.5f == 0.f);
+  const bool no_region = CS && ((ng == 0) || ((gt[0] + gt[2]) * 0.5f == 0.f));
   for (int g = 0; g < ng; ++g) {
     const float x1 = gt[g * 4 + 0], y1 = gt[g * 4 + 1], x2 = gt[g * 4 + 2], y2 = gt[g * 4 + 3];
     const float l = x - x1, t = y - y1, r = x2 - x, b = y2 - y;
     if (g == 0) { out.l = l; out.t = t; out.r = r; out.b = b; }   // argmin over all-INF rows is index 0
     if (no_region) continue;
-    const float cx = (x1 + x2) * 0.5f, cy = (y1 + y2) * 0.5f;
-    const float xmin = cx - lv.radius_px, ymin = cy - lv.radius_px, xmax = cx + lv.radius_px, ymax = cy + lv.radius_px;
-    const float c1 = xmin > x1 ? xmin : x1, c2 = ymin > y1 ? ymin : y1;
-    const float c3 = xmax > x2 ? x2 : xmax, c4 = ymax > y2 ? y2 : ymax;
-    const bool inside = fminf(fminf(x - c1, y - c2), fminf(c3 - x, c4 - y)) > 0.f;
+    bool inside;
+    if (CS) {
+      const float cx = (x1 + x2) * 0.5f, cy = (y1 + y2) * 0.5f;
+      const float xmin = cx - lv.radius_px, ymin = cy - lv.radius_px, xmax = cx + lv.radius_px, ymax = cy + lv.radius_px;
+      const float c1 = xmin > x1 ? xmin : x1, c2 = ymin > y1 ? ymin : y1;
+      const float c3 = xmax > x2 ? x2 : xmax, c4 = ymax > y2 ? y2 : ymax;
+      inside = fminf(fminf(x - c1, y - c2), fminf(c3 - x, c4 - y)) > 0.f;
+    } else {
+      inside = fminf(fminf(l, t), fminf(r, b)) > 0.f;
+    }
     const float mx = fmaxf(fmaxf(l, t), fmaxf(r, b));
     const bool cared = (mx >= lv.lo) && (mx <= lv.hi);
     const float area = (x2 - x1 + 1.f) * (y2 - y1 + 1.f);
@@ -66,15 +77,16 @@ __device__ __forceinline__ float focal_grad(float x, int label, float gamma, flo
   return -(1.f - alpha) * powf(p, gamma) * ((-1.f * x * ge - logf(1.f + expf(x - 2.f * x * ge))) * (1.f - p) * gamma - p);
 }
 
-// GIoU loss 1 - giou and its gradient w.r.t. the predicted distances (layers/iou_loss.py:10-43)
-__device__ __forceinline__ float giou_loss(const float pd[4], const Target& tg, float grad[4]) {
+// regression loss of one positive location and its gradient w.r.t. the predicted distances (layers/iou_loss.py:10-43), LT =
+// FCOS.LOC_LOSS_TYPE: 1 - giou (:40-41), -log(iou) (:36-37) or 1 - iou (:38-39), iou = (I + 1) / (U + 1) (:34)
+template <int LT>
+__device__ __forceinline__ float loc_loss(const float pd[4], const Target& tg, float grad[4]) {
   const float pl = pd[0], pt = pd[1], pr = pd[2], pb = pd[3];
   const float ta = (tg.l + tg.r) * (tg.t + tg.b), pa = (pl + pr) * (pt + pb);
   const float wi = fminf(pl, tg.l) + fminf(pr, tg.r), gw = fmaxf(pl, tg.l) + fmaxf(pr, tg.r);
   const float hi = fminf(pb, tg.b) + fminf(pt, tg.t), gh = fmaxf(pb, tg.b) + fmaxf(pt, tg.t);
   const float ac = gw * gh + 1e-7f, ai = wi * hi, au = ta + pa - ai;
   const float iou = (ai + 1.f) / (au + 1.f);
-  const float giou = iou - (ac - au) / ac;
   if (grad) {
     // d/dp of min(p,t) is 1 when p < t (0.5 on ties, as autograd), of max(p,t) 1 when p > t
     const float tt[4] = {tg.l, tg.t, tg.r, tg.b};
@@ -88,14 +100,24 @@ __device__ __forceinline__ float giou_loss(const float pd[4], const Target& tg, 
       const float dpa = horiz ? (pt + pb) : (pl + pr);
       const float dau = dpa - dai;
       const float diou = (dai * (au + 1.f) - (ai + 1.f) * dau) / ((au + 1.f) * (au + 1.f));
-      const float dgiou = diou + (dau * ac - au * dac) / (ac * ac);
-      grad[k] = -dgiou;
+      if (LT == OSD_LOC_LOSS_GIOU) {
+        const float dgiou = diou + (dau * ac - au * dac) / (ac * ac);
+        grad[k] = -dgiou;
+      } else if (LT == OSD_LOC_LOSS_IOU) {
+        grad[k] = -diou / iou;
+      } else {
+        grad[k] = -diou;
+      }
     }
   }
-  return 1.f - giou;
+  if (LT == OSD_LOC_LOSS_GIOU) {
+    const float giou = iou - (ac - au) / ac;
+    return 1.f - giou;
+  }
+  return LT == OSD_LOC_LOSS_IOU ? -logf(iou) : 1.f - iou;
 }
 
-template <typename T, int PHASE>
+template <typename T, int PHASE, bool CS, int LT>
 __device__ __forceinline__ void fcos_loss_body(const T* __restrict__ cls_ctr, const T* __restrict__ reg,
                                                         const float* __restrict__ gt, const int* __restrict__ gt_count,
                                                         int max_gt, LossLevel lv, int n_images, float gamma, float alpha,
@@ -119,7 +141,7 @@ __device__ __forceinline__ void fcos_loss_body(const T* __restrict__ cls_ctr, co
   for (int i = bx * blockDim.x + threadIdx.x; i < hw; i += nbx * blockDim.x) {
     const int yy = i / lv.w, xx = i - yy * lv.w;
     const float x = (float)(xx * lv.stride + lv.stride / 2), y = (float)(yy * lv.stride + lv.stride / 2);
-    const Target tg = assign_target(x, y, g, ng, lv);
+    const Target tg = assign_target<CS>(x, y, g, ng, lv);
     const size_t pix = (size_t)img * hw + i;
     const float logit = to_f32(cls_ctr[pix * 4 + 0]);
     if (PHASE == 0) {
@@ -130,7 +152,7 @@ __device__ __forceinline__ void fcos_loss_body(const T* __restrict__ cls_ctr, co
         const float c = to_f32(cls_ctr[pix * 4 + 1]);
         acc[0] += 1.f;
         acc[1] += wgt;
-        acc[3] += wgt * giou_loss(pd, tg, nullptr);
+        acc[3] += wgt * loc_loss<LT>(pd, tg, nullptr);
         acc[4] += fmaxf(c, 0.f) - c * wgt + log1pf(expf(-fabsf(c)));        // BCEWithLogits
       }
     } else {
@@ -141,7 +163,7 @@ __device__ __forceinline__ void fcos_loss_body(const T* __restrict__ cls_ctr, co
         const float wgt = sqrtf((fminf(tg.l, tg.r) / fmaxf(tg.l, tg.r)) * (fminf(tg.t, tg.b) / fmaxf(tg.t, tg.b)));
         const float c = to_f32(cls_ctr[pix * 4 + 1]);
         float gg[4];
-        giou_loss(pd, tg, gg);
+        loc_loss<LT>(pd, tg, gg);
         const float wsel = sums[1] > 0.f ? wgt : 1.f;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
@@ -188,15 +210,15 @@ __device__ __forceinline__ void fcos_loss_body(const T* __restrict__ cls_ctr, co
   }
 }
 
-template <typename T, int PHASE>
+template <typename T, int PHASE, bool CS, int LT>
 __global__ void __launch_bounds__(256) fcos_loss_kernel(const T* __restrict__ cls_ctr, const T* __restrict__ reg,
                                                         const float* __restrict__ gt, const int* __restrict__ gt_count,
                                                         int max_gt, LossLevel lv, int n_images, float gamma, float alpha,
                                                         const float* __restrict__ scale_dev, float* __restrict__ sums,
                                                         T* __restrict__ d_cls_ctr, T* __restrict__ d_reg, int gstride,
                                                         float* __restrict__ d_scale_raw) {
-  fcos_loss_body<T, PHASE>(cls_ctr, reg, gt, gt_count, max_gt, lv, n_images, gamma, alpha, scale_dev, sums, d_cls_ctr, d_reg,
-                           gstride, d_scale_raw, blockIdx.x, gridDim.x);
+  fcos_loss_body<T, PHASE, CS, LT>(cls_ctr, reg, gt, gt_count, max_gt, lv, n_images, gamma, alpha, scale_dev, sums, d_cls_ctr, d_reg,
+                                   gstride, d_scale_raw, blockIdx.x, gridDim.x);
 }
 
 // all FPN levels in one launch: blockIdx.z = level (the per-level launches sit on the critical path between forward and
@@ -209,7 +231,7 @@ struct LossLevels {
   int nbx[kLossLevels];
 };
 
-template <typename T, int PHASE>
+template <typename T, int PHASE, bool CS, int LT>
 __global__ void __launch_bounds__(256) fcos_loss_levels_kernel(LossLevels L, const float* __restrict__ gt,
                                                                const int* __restrict__ gt_count, int max_gt, int n_images,
                                                                float gamma, float alpha, float* __restrict__ sums, int gstride) {
@@ -222,7 +244,7 @@ __global__ void __launch_bounds__(256) fcos_loss_levels_kernel(LossLevels L, con
       sd = L.scale_dev[i]; dsr = L.d_scale_raw[i]; lv = L.lv[i]; nbx = L.nbx[i];
     }
   if ((int)blockIdx.x >= nbx) return;
-  fcos_loss_body<T, PHASE>(cc, rg, gt, gt_count, max_gt, lv, n_images, gamma, alpha, sd, sums, dcc, drg, gstride, dsr, blockIdx.x, nbx);
+  fcos_loss_body<T, PHASE, CS, LT>(cc, rg, gt, gt_count, max_gt, lv, n_images, gamma, alpha, sd, sums, dcc, drg, gstride, dsr, blockIdx.x, nbx);
 }
 
 // (raw, scales, gscales: optional — the gradient of the learnable per-level Scale, fcos.py:81: gscales[l] += raw[l] / scales[l], which was
@@ -244,12 +266,29 @@ __global__ void fcos_loss_finalize_kernel(const float* __restrict__ sums, float*
 
 #define OSD_STREAM(s) reinterpret_cast<hipStream_t>(s)
 
+// run LAUNCH(TT, PH, CS, LT) for the (dtype, phase, center_sample, loc_loss_type) of the call: every mode is an instantiation of its own
+#define OSD_LOSS_BY_LT(LAUNCH, TT, PH, CS)                                     \
+  do {                                                                         \
+    if (loc_loss_type == OSD_LOC_LOSS_GIOU) LAUNCH(TT, PH, CS, OSD_LOC_LOSS_GIOU); \
+    else if (loc_loss_type == OSD_LOC_LOSS_IOU) LAUNCH(TT, PH, CS, OSD_LOC_LOSS_IOU); \
+    else LAUNCH(TT, PH, CS, OSD_LOC_LOSS_LINEAR_IOU);                          \
+  } while (0)
+#define OSD_LOSS_BY_MODE(LAUNCH, TT)                                           \
+  do {                                                                         \
+    if (phase == 0) { if (center_sample) OSD_LOSS_BY_LT(LAUNCH, TT, 0, true); else OSD_LOSS_BY_LT(LAUNCH, TT, 0, false); } \
+    else { if (center_sample) OSD_LOSS_BY_LT(LAUNCH, TT, 1, true); else OSD_LOSS_BY_LT(LAUNCH, TT, 1, false); }            \
+  } while (0)
+
+static bool loc_loss_type_ok(int t) { return t == OSD_LOC_LOSS_GIOU || t == OSD_LOC_LOSS_IOU || t == OSD_LOC_LOSS_LINEAR_IOU; }
+
 // phase 0: accumulate `sums[5]` (caller zeroes them once before the first level); phase 1: gradients.
-extern "C" int osd_fcos_loss_level(int phase, const void* cls_ctr, const void* reg, const float* gt_boxes,
-                                   const int32_t* gt_count, int max_gt, int n, int h, int w, int stride, float size_lo,
-                                   float size_hi, float radius, float gamma, float alpha, const float* scale_dev,
-                                   float* sums, void* d_cls_ctr, void* d_reg, int grad_stride, float* d_scale_raw,
-                                   int dtype, void* stream) {
+// center_sample / loc_loss_type: FCOS.CENTER_SAMPLE / FCOS.LOC_LOSS_TYPE (OSD_LOC_LOSS_*)
+extern "C" int osd_fcos_loss_level_opt(int phase, const void* cls_ctr, const void* reg, const float* gt_boxes,
+                                       const int32_t* gt_count, int max_gt, int n, int h, int w, int stride, float size_lo,
+                                       float size_hi, float radius, float gamma, float alpha, const float* scale_dev,
+                                       float* sums, void* d_cls_ctr, void* d_reg, int grad_stride, float* d_scale_raw,
+                                       int dtype, int center_sample, int loc_loss_type, void* stream) {
+  if (!loc_loss_type_ok(loc_loss_type)) return osd_fail(OSD_ERR_INVALID_ARG, "fcos_loss: bad loc_loss_type %d", loc_loss_type);
   if (!cls_ctr || !reg || !gt_boxes || !gt_count || !sums) return osd_fail(OSD_ERR_INVALID_ARG, "fcos_loss: null argument");
   if (phase == 1 && (!d_cls_ctr || !d_reg || !d_scale_raw || grad_stride < 4))
     return osd_fail(OSD_ERR_INVALID_ARG, "fcos_loss: bad gradient output");
@@ -259,15 +298,25 @@ extern "C" int osd_fcos_loss_level(int phase, const void* cls_ctr, const void* r
   int bx = cdiv(h * w, 256);
   if (bx > 256) bx = 256;
   dim3 grid(bx, n);
-#define OSD_LOSS_LAUNCH(TT, PH)                                                                                           \
-  hipLaunchKernelGGL((fcos_loss_kernel<TT, PH>), grid, dim3(256), 0, OSD_STREAM(stream), (const TT*)cls_ctr, (const TT*)reg, \
+#define OSD_LOSS_LAUNCH(TT, PH, CS, LT)                                                                                   \
+  hipLaunchKernelGGL((fcos_loss_kernel<TT, PH, CS, LT>), grid, dim3(256), 0, OSD_STREAM(stream), (const TT*)cls_ctr, (const TT*)reg, \
                      gt_boxes, gt_count, max_gt, lv, n, gamma, alpha, scale_dev, sums, (TT*)d_cls_ctr, (TT*)d_reg, grad_stride, \
                      d_scale_raw)
-  if (dtype == OSD_F32) { if (phase == 0) OSD_LOSS_LAUNCH(float, 0); else OSD_LOSS_LAUNCH(float, 1); }
-  else if (dtype == OSD_BF16) { if (phase == 0) OSD_LOSS_LAUNCH(__bf16, 0); else OSD_LOSS_LAUNCH(__bf16, 1); }
+  if (dtype == OSD_F32) OSD_LOSS_BY_MODE(OSD_LOSS_LAUNCH, float);
+  else if (dtype == OSD_BF16) OSD_LOSS_BY_MODE(OSD_LOSS_LAUNCH, __bf16);
   else return osd_fail(OSD_ERR_INVALID_ARG, "fcos_loss: bad dtype");
 #undef OSD_LOSS_LAUNCH
   return osd_check_launch("fcos_loss_level");
+}
+
+extern "C" int osd_fcos_loss_level(int phase, const void* cls_ctr, const void* reg, const float* gt_boxes,
+                                   const int32_t* gt_count, int max_gt, int n, int h, int w, int stride, float size_lo,
+                                   float size_hi, float radius, float gamma, float alpha, const float* scale_dev,
+                                   float* sums, void* d_cls_ctr, void* d_reg, int grad_stride, float* d_scale_raw,
+                                   int dtype, void* stream) {
+  return osd_fcos_loss_level_opt(phase, cls_ctr, reg, gt_boxes, gt_count, max_gt, n, h, w, stride, size_lo, size_hi, radius, gamma,
+                                 alpha, scale_dev, sums, d_cls_ctr, d_reg, grad_stride, d_scale_raw, dtype, 1, OSD_LOC_LOSS_GIOU,
+                                 stream);
 }
 
 // losses[4] = {loss_cls, loss_reg, loss_centerness, num_pos} from the accumulated sums
@@ -288,12 +337,14 @@ extern "C" int osd_fcos_loss_finalize_scales(const float* sums, float* losses, i
 }
 
 // every FPN level in one launch per phase (phase 0: sums; phase 1: gradients).  Host arrays of n_levels entries.
-extern "C" int osd_fcos_loss_levels(int phase, int n_levels, const void* const* cls_ctrs, const void* const* regs,
-                                    const float* gt_boxes, const int32_t* gt_count, int max_gt, int n, const int32_t* hs,
-                                    const int32_t* ws, const int32_t* strides, const float* size_lo, const float* size_hi,
-                                    float radius, float gamma, float alpha, const float* const* scale_devs, float* sums,
-                                    void* const* d_cls_ctrs, void* const* d_regs, int grad_stride,
-                                    float* const* d_scale_raws, int dtype, void* stream) {
+extern "C" int osd_fcos_loss_levels_opt(int phase, int n_levels, const void* const* cls_ctrs, const void* const* regs,
+                                        const float* gt_boxes, const int32_t* gt_count, int max_gt, int n, const int32_t* hs,
+                                        const int32_t* ws, const int32_t* strides, const float* size_lo, const float* size_hi,
+                                        float radius, float gamma, float alpha, const float* const* scale_devs, float* sums,
+                                        void* const* d_cls_ctrs, void* const* d_regs, int grad_stride,
+                                        float* const* d_scale_raws, int dtype, int center_sample, int loc_loss_type,
+                                        void* stream) {
+  if (!loc_loss_type_ok(loc_loss_type)) return osd_fail(OSD_ERR_INVALID_ARG, "fcos_loss_levels: bad loc_loss_type %d", loc_loss_type);
   if (!cls_ctrs || !regs || !gt_boxes || !gt_count || !sums || !hs || !ws || !strides || !size_lo || !size_hi ||
       n_levels < 1 || n_levels > kLossLevels)
     return osd_fail(OSD_ERR_INVALID_ARG, "fcos_loss_levels: bad arguments");
@@ -316,12 +367,23 @@ extern "C" int osd_fcos_loss_levels(int phase, int n_levels, const void* const* 
     if (i < n_levels && bx > bmax) bmax = bx;
   }
   dim3 grid(bmax, n, n_levels);
-#define OSD_LOSSL_LAUNCH(TT, PH)                                                                                       \
-  hipLaunchKernelGGL((fcos_loss_levels_kernel<TT, PH>), grid, dim3(256), 0, OSD_STREAM(stream), L, gt_boxes, gt_count, max_gt, n, \
+#define OSD_LOSSL_LAUNCH(TT, PH, CS, LT)                                                                               \
+  hipLaunchKernelGGL((fcos_loss_levels_kernel<TT, PH, CS, LT>), grid, dim3(256), 0, OSD_STREAM(stream), L, gt_boxes, gt_count, max_gt, n, \
                      gamma, alpha, sums, grad_stride)
-  if (dtype == OSD_F32) { if (phase == 0) OSD_LOSSL_LAUNCH(float, 0); else OSD_LOSSL_LAUNCH(float, 1); }
-  else if (dtype == OSD_BF16) { if (phase == 0) OSD_LOSSL_LAUNCH(__bf16, 0); else OSD_LOSSL_LAUNCH(__bf16, 1); }
+  if (dtype == OSD_F32) OSD_LOSS_BY_MODE(OSD_LOSSL_LAUNCH, float);
+  else if (dtype == OSD_BF16) OSD_LOSS_BY_MODE(OSD_LOSSL_LAUNCH, __bf16);
   else return osd_fail(OSD_ERR_INVALID_ARG, "fcos_loss_levels: bad dtype");
 #undef OSD_LOSSL_LAUNCH
   return osd_check_launch("fcos_loss_levels");
+}
+
+extern "C" int osd_fcos_loss_levels(int phase, int n_levels, const void* const* cls_ctrs, const void* const* regs,
+                                    const float* gt_boxes, const int32_t* gt_count, int max_gt, int n, const int32_t* hs,
+                                    const int32_t* ws, const int32_t* strides, const float* size_lo, const float* size_hi,
+                                    float radius, float gamma, float alpha, const float* const* scale_devs, float* sums,
+                                    void* const* d_cls_ctrs, void* const* d_regs, int grad_stride,
+                                    float* const* d_scale_raws, int dtype, void* stream) {
+  return osd_fcos_loss_levels_opt(phase, n_levels, cls_ctrs, regs, gt_boxes, gt_count, max_gt, n, hs, ws, strides, size_lo, size_hi,
+                                  radius, gamma, alpha, scale_devs, sums, d_cls_ctrs, d_regs, grad_stride, d_scale_raws, dtype, 1,
+                                  OSD_LOC_LOSS_GIOU, stream);
 }

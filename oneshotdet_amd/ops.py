@@ -5,7 +5,7 @@ import os
 
 import torch
 
-from . import _lib
+from . import _lib, spec
 from ._lib import (ACT_EXP_SCALE, ACT_NONE, ACT_RELU, GN_SPLITS, OSD_BF16, OSD_F32, RES_DOWN2X, RES_NONE, RES_SAME, RES_UP2X,
                    ConvDesc)
 
@@ -1070,13 +1070,22 @@ def groupnorm_relu_bwd(u, dt, ab, gamma, beta, dgamma, dbeta, groups=32):
     return groupnorm_relu_bwd_levels([u], [dt], ab, gamma, beta, dgamma, dbeta, groups)[0]
 
 
+def _loss_mode(center_sample, loc_loss_type):
+    """(FCOS.CENTER_SAMPLE, FCOS.LOC_LOSS_TYPE) -> the C boundary's (int, OSD_LOC_LOSS_*); ValueError for an unknown loss"""
+    cs, lt = spec.loss_mode(center_sample, loc_loss_type)
+    return int(cs), spec.LOC_LOSS_TYPES.index(lt)
+
+
 def fcos_loss_level(phase, cls_ctr, reg, gt_boxes, gt_count, stride, size_lo, size_hi, radius, gamma, alpha, scale_dev,
-                    sums, d_cls_ctr=None, d_reg=None, d_scale_raw=None):
+                    sums, d_cls_ctr=None, d_reg=None, d_scale_raw=None, center_sample=True, loc_loss_type="giou"):
+    """One FPN level of the FCOS loss (phase 0: sums, phase 1: gradients).  center_sample / loc_loss_type: FCOS.CENTER_SAMPLE
+    (False: positives inside the whole box, loss.py:176-177) / FCOS.LOC_LOSS_TYPE ("giou", "iou", "linear_iou"; iou_loss.py:34-41)."""
+    cs, lt = _loss_mode(center_sample, loc_loss_type)
     n, h, w, _ = cls_ctr.shape
     gs = d_cls_ctr.shape[-1] if d_cls_ctr is not None else 4
-    _lib.call("osd_fcos_loss_level", phase, _p(cls_ctr), _p(reg), _p(gt_boxes), _p(gt_count), gt_boxes.shape[1], n,
+    _lib.call("osd_fcos_loss_level_opt", phase, _p(cls_ctr), _p(reg), _p(gt_boxes), _p(gt_count), gt_boxes.shape[1], n,
               h, w, stride, float(size_lo), float(size_hi), float(radius), float(gamma), float(alpha), _p(scale_dev),
-              _p(sums), _p(d_cls_ctr), _p(d_reg), gs, _p(d_scale_raw), _dt(cls_ctr), _stream())
+              _p(sums), _p(d_cls_ctr), _p(d_reg), gs, _p(d_scale_raw), _dt(cls_ctr), cs, lt, _stream())
 
 
 def _ptr_array(tensors):
@@ -1084,8 +1093,9 @@ def _ptr_array(tensors):
 
 
 def fcos_loss_levels(phase, head_out, gt_boxes, gt_count, strides, size_ranges, radius, gamma, alpha, scale_devs, sums,
-                     d_cls_ctrs=None, d_regs=None, d_scale_raws=None):
+                     d_cls_ctrs=None, d_regs=None, d_scale_raws=None, center_sample=True, loc_loss_type="giou"):
     """fcos_loss_level for every FPN level in ONE launch.  head_out: [(cls_ctr, reg)] per level."""
+    cs, lt = _loss_mode(center_sample, loc_loss_type)
     k = len(head_out)
     n = head_out[0][0].shape[0]
     gs = d_cls_ctrs[0].shape[-1] if d_cls_ctrs is not None else 4
@@ -1095,13 +1105,14 @@ def fcos_loss_levels(phase, head_out, gt_boxes, gt_count, strides, size_ranges, 
     lo = (C.c_float * k)(*[float(a) for a, _ in size_ranges])
     hi = (C.c_float * k)(*[float(b) for _, b in size_ranges])
     none = C.c_void_p(0)
-    _lib.call("osd_fcos_loss_levels", phase, k, _ptr_array([c for c, _ in head_out]), _ptr_array([r for _, r in head_out]),
+    _lib.call("osd_fcos_loss_levels_opt", phase, k, _ptr_array([c for c, _ in head_out]), _ptr_array([r for _, r in head_out]),
               _p(gt_boxes), _p(gt_count), gt_boxes.shape[1], n, hs, ws, st, lo, hi, float(radius), float(gamma), float(alpha),
               _ptr_array(scale_devs) if scale_devs is not None else none, _p(sums),
               _ptr_array(d_cls_ctrs) if d_cls_ctrs is not None else none, _ptr_array(d_regs) if d_regs is not None else none,
-              gs, _ptr_array(d_scale_raws) if d_scale_raws is not None else none, _dt(head_out[0][0]), _stream())
+              gs, _ptr_array(d_scale_raws) if d_scale_raws is not None else none, _dt(head_out[0][0]), cs, lt, _stream())
     _rec("fcos_loss", phase=phase, head_out=list(head_out), gt_boxes=gt_boxes, gt_count=gt_count, gamma=float(gamma), alpha=float(alpha),
-         scale_devs=scale_devs, sums=sums, d_cls_ctrs=d_cls_ctrs, d_regs=d_regs, d_scale_raws=d_scale_raws)
+         scale_devs=scale_devs, sums=sums, d_cls_ctrs=d_cls_ctrs, d_regs=d_regs, d_scale_raws=d_scale_raws,
+         center_sample=bool(cs), loc_loss_type=spec.LOC_LOSS_TYPES[lt])
 
 
 def gn_fwd_ws_parts(ws, k, n, groups=32):

@@ -29,6 +29,9 @@ FREEZE_CONV_BODY_AT = 2               # stem + layer1 frozen (resnet.py:127-136)
 LOSS_ALPHA = 0.25
 LOSS_GAMMA = 2.0
 POS_RADIUS = 1.5
+CENTER_SAMPLE = True                  # yaml FCOS.CENTER_SAMPLE (defaults.py:309 has False: positives inside the whole box, loss.py:176-177)
+LOC_LOSS_TYPE = "giou"                # yaml FCOS.LOC_LOSS_TYPE (defaults.py:311 has 'iou'; iou_loss.py:36-41 also 'linear_iou')
+LOC_LOSS_TYPES = ("giou", "iou", "linear_iou")       # index = OSD_LOC_LOSS_* of include/oneshotdet_hip.h
 SIZE_DIVISIBILITY = 32
 INF = 100000000
 # second stage: yaml ROI_BOX_HEAD + defaults.py:196-229,511
@@ -48,6 +51,13 @@ BOX_LOSS_WEIGHTS = (5.0, 2.5)         # loss_classifier *= 5; loss_box_reg *= 2.
 LEVEL_MAP_SCALE = 224                 # poolers.py:16 LevelMapper canonical_scale / canonical_level / eps
 LEVEL_MAP_LEVEL = 4
 LEVEL_MAP_EPS = 1e-6
+
+
+def loss_mode(center_sample, loc_loss_type):
+    """-> (bool, str) of the two FCOS loss options, ValueError for a regression loss iou_loss.py:34-43 does not have."""
+    if loc_loss_type not in LOC_LOSS_TYPES:
+        raise ValueError("loc_loss_type must be one of %s (FCOS.LOC_LOSS_TYPE), not %r" % (", ".join(LOC_LOSS_TYPES), loc_loss_type))
+    return bool(center_sample), str(loc_loss_type)
 
 
 def _bn(prefix, n, out):

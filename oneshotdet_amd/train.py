@@ -19,6 +19,11 @@ into the one dW (BackwardPass._flush_shared_stage).
 
 supp_roialign=False (FEW_SHOT.SUPP_ROIALIGN False, generalized_rcnn.py:87-94, 302-303): the query pyramid is pooled by global
 average (ops.query_avgpool_levels) instead of the 1 x 1 ROIAlign of each query's box, in the forward and in the pooling backward.
+
+center_sample / loc_loss_type (FCOS.CENTER_SAMPLE / FCOS.LOC_LOSS_TYPE, fcos/loss.py:168-177, layers/iou_loss.py:34-41): which
+locations are positive (True: inside a box's sampling region; False: inside the whole box) and the regression loss ("giou", "iou" =
+-log(iou), "linear_iou" = 1 - iou).  The defaults (True, "giou") are the config of record; the reference's own defaults are
+(False, "iou").  Only the loss kernels' instantiation changes: the step has the same launches in every mode.
 """
 import math
 import os
@@ -85,7 +90,9 @@ class TConv(object):
 class TrainEngine(ForwardPass, BackwardPass, SecondStage, Update, State):
     def __init__(self, state_dict, dtype=torch.bfloat16, device="cuda", lr=0.0005, momentum=0.9, weight_decay=0.0001,
                  process_group=None, wgrad_side_stream=True, optimizer="fused", second_stage=False, ordered_wgrad=None,
-                 exchange_single_rank=False, grad_wire_dtype=None, siamese_backbone=True, supp_roialign=True):
+                 exchange_single_rank=False, grad_wire_dtype=None, siamese_backbone=True, supp_roialign=True,
+                 center_sample=True, loc_loss_type="giou"):
+        self.center_sample, self.loc_loss_type = spec.loss_mode(center_sample, loc_loss_type)     # ValueError before anything is built
         if not torch.cuda.is_available():
             raise ops._lib.OsdError("TrainEngine needs an MI355X: no GPU visible and there is no CPU fallback")
         ops._lib.load()

@@ -207,7 +207,8 @@ class ForwardPass(object):
         sums = zbuf[:8]
         nl = len(head_out)
         ops.fcos_loss_levels(0, head_out, gt_boxes, gt_count, spec.FPN_STRIDES[:nl], SIZE_RANGES[:nl], spec.POS_RADIUS,
-                             spec.LOSS_GAMMA, spec.LOSS_ALPHA, None, sums)
+                             spec.LOSS_GAMMA, spec.LOSS_ALPHA, None, sums, center_sample=self.center_sample,
+                             loc_loss_type=self.loc_loss_type)
         gstride = self.convs[h + "bbox_pred"].pd.cin_k
         grads = []
         raw = zbuf[8:8 + max(nl, 5)]
@@ -222,11 +223,13 @@ class ForwardPass(object):
             grads.append(self._pred_grad_bufs[key])
         ops.fcos_loss_levels(1, head_out, gt_boxes, gt_count, spec.FPN_STRIDES[:nl], SIZE_RANGES[:nl], spec.POS_RADIUS,
                              spec.LOSS_GAMMA, spec.LOSS_ALPHA, [scales[l:l + 1] for l in range(nl)], sums,
-                             [g[0] for g in grads], [g[1] for g in grads], [raw[l:l + 1] for l in range(nl)])
+                             [g[0] for g in grads], [g[1] for g in grads], [raw[l:l + 1] for l in range(nl)],
+                             center_sample=self.center_sample, loc_loss_type=self.loc_loss_type)
         losses = torch.empty(4, device=self.device, dtype=torch.float32)
         # the losses, and d loss / d scale_l = sum ds * x, x = log(reg) / scale_l: gscales += raw / scales in the same launch
         ops._lib.call("osd_fcos_loss_finalize_scales", ops._p(sums), ops._p(losses), n, ops._p(raw), ops._p(scales), ops._p(gscales), nl,
                       ops._stream())
-        # {num_pos, sum_w, sum_focal, sum_w*(1-giou), sum_bce}: the un-normalised sums are additive over images (tests)
+        # {num_pos, sum_w, sum_focal, sum_w*loc_loss, sum_bce}, loc_loss = 1 - giou / -log(iou) / 1 - iou by self.loc_loss_type: the
+        # un-normalised sums are additive over images (tests)
         self.last_loss_sums = sums
         return losses, grads

@@ -1,0 +1,290 @@
+"""GPU (-m gpu): the FCOS loss kernels in the reference's other modes (center_sample=False: FCOS.CENTER_SAMPLE False,
+fcos/loss.py:176-177; loc_loss_type "iou" / "linear_iou": FCOS.LOC_LOSS_TYPE, layers/iou_loss.py:34-41), all six combinations,
+fp32 and bf16, through the per-level and the all-levels entry, against fcos_loss_modes.npz — recorded through the real reference
+by tests/golden/make_golden_fcos_loss.py: its losses, its num_pos, its autograd gradients.
+
+Bounds are the project's existing ones for the same quantities: losses rtol 1e-4 fp32 / 3e-2 bf16 (test_gpu_train), num_pos
+exact, stored gradients by oracle.launch_replay.compare as test_gpu_launch_replay applies it to `fcos_loss_grad` (bf16: within one
+unit in the last place of the rounded reference, at most 2 % of a tensor's elements off it; fp32: 1e-4 relative + 1e-5 x absmax).
+The fixture's inputs are bfloat16 values, so both dtypes are given the same numbers and the bf16 run differs from the fp32 one
+only in how its gradients are stored: -log(iou) needs no bound of its own.  The reference's gradient w.r.t. bbox_reg (the head's
+output after exp) is carried to the bbox_pred conv's output x, reg = exp(scale * x), here: d/dx = d/dreg * reg * scale, and the
+Scale's raw gradient is sum d/dreg * reg * log(reg) (fcos.py:95-97), as oracle/launch_replay.fcos_loss_grad_launch does.  That
+raw sum is an fp32 accumulation in both dtypes of at most ~1100 terms, each good to ~1e-6 relative (logf, the quotient rule),
+added by atomics in any order: it is held to 1e-4 x sum |terms|."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+import fcos_loss_ref as flr
+import golden_utils as gu
+from oneshotdet_amd import spec, synth
+from oracle import launch_replay as lr
+
+pytestmark = pytest.mark.gpu
+DT = {"f32": torch.float32, "bf16": torch.bfloat16}
+LOSS_RTOL = {"f32": 1e-4, "bf16": 3e-2}
+FLIP_CAP = 0.02
+SCALES = (1.0, 0.75, 1.25, 0.5, 1.5)
+GSTRIDE = 8            # the gradient buffers' channel stride (the data-gradient convs' K padding): only [0, 4) is written
+CASES = ("quirks", "random")
+
+
+class Inputs(object):
+    """A fixture case on the device, in the kernels' layout: per level cls_ctr [N, h, w, 4] (logit, centerness, 0, 0) and
+    reg [N, h, w, 4] (after exp)."""
+
+    def __init__(self, f, name, dt, images=None):
+        self.hw = [tuple(int(v) for v in r) for r in f[name + ".hw"]]
+        gb = f[name + ".gt_boxes"]
+        self.N_all = int(gb[:, 0].max()) + 1
+        self.images = list(range(self.N_all)) if images is None else list(images)
+        self.gts = [gb[gb[:, 0] == i, 1:] for i in self.images]
+        N = self.N = len(self.images)
+        G = max(len(g) for g in self.gts)
+        gtb = torch.zeros(N, max(G, 1), 4)
+        for i, g in enumerate(self.gts):
+            gtb[i, :len(g)] = torch.from_numpy(g)
+        self.gtb = gtb.cuda()
+        self.cnt = torch.tensor([len(g) for g in self.gts], dtype=torch.int32).cuda()
+        self.head, self.flat_reg = [], []
+        beg = 0
+        for h, w in self.hw:
+            n = self.N_all * h * w
+            sel = torch.tensor(self.images)
+            lg = torch.from_numpy(f[name + ".logits"][beg:beg + n]).reshape(self.N_all, h, w, 1)[sel]
+            ct = torch.from_numpy(f[name + ".centerness"][beg:beg + n]).reshape(self.N_all, h, w, 1)[sel]
+            rg = torch.from_numpy(f[name + ".bbox_reg"][beg:beg + n]).reshape(self.N_all, h, w, 4)[sel]
+            cc = torch.cat([lg, ct, torch.zeros(N, h, w, 2)], 3)
+            self.head.append((cc.to(DT[dt]).cuda().contiguous(), rg.to(DT[dt]).cuda().contiguous()))
+            assert torch.equal(self.head[-1][1].float().cpu(), rg)          # bfloat16 values: nothing is lost in either dtype
+            self.flat_reg.append(rg)
+            beg += n
+        self.scales = torch.tensor(SCALES[:len(self.hw)], dtype=torch.float32).cuda()
+        self.dt = dt
+
+    def per_level(self, flat, c):
+        """a level-first fixture array [P(, c)] -> per level [N_all, h, w, c]"""
+        out, beg = [], 0
+        t = torch.from_numpy(np.asarray(flat)).reshape(-1, c)
+        for h, w in self.hw:
+            n = self.N_all * h * w
+            out.append(t[beg:beg + n].reshape(self.N_all, h, w, c))
+            beg += n
+        return out
+
+
+def run_kernels(inp, entry, center_sample, loc_loss_type, old_symbol=False):
+    """-> losses [4] (cpu), sums [5], per level (d_cls_ctr, d_reg) and the Scale's raw gradient per level"""
+    from oneshotdet_amd import _lib, ops
+    from oneshotdet_amd.train_forward import SIZE_RANGES
+    nl = len(inp.hw)
+    zbuf = torch.zeros(16, device="cuda", dtype=torch.float32)
+    sums, raw = zbuf[:8], zbuf[8:8 + nl]
+    grads = [(torch.zeros(cc.shape[:3] + (GSTRIDE,), device="cuda", dtype=cc.dtype),
+              torch.zeros(cc.shape[:3] + (GSTRIDE,), device="cuda", dtype=cc.dtype)) for cc, _ in inp.head]
+    sc = [inp.scales[l:l + 1] for l in range(nl)]
+    mode = dict(center_sample=center_sample, loc_loss_type=loc_loss_type)
+    if old_symbol:
+        assert (center_sample, loc_loss_type) == (True, "giou")
+        k, n = nl, inp.N
+        hs = (C.c_int32 * k)(*[h for h, _ in inp.hw])
+        ws = (C.c_int32 * k)(*[w for _, w in inp.hw])
+        st = (C.c_int32 * k)(*spec.FPN_STRIDES[:k])
+        lo = (C.c_float * k)(*[float(a) for a, _ in SIZE_RANGES[:k]])
+        hi = (C.c_float * k)(*[float(b) for _, b in SIZE_RANGES[:k]])
+        pa = ops._ptr_array
+        for phase in (0, 1):
+            _lib.call("osd_fcos_loss_levels", phase, k, pa([c for c, _ in inp.head]), pa([r for _, r in inp.head]), ops._p(inp.gtb),
+                      ops._p(inp.cnt), inp.gtb.shape[1], n, hs, ws, st, lo, hi, float(spec.POS_RADIUS), float(spec.LOSS_GAMMA),
+                      float(spec.LOSS_ALPHA), pa(sc), ops._p(sums), pa([g[0] for g in grads]), pa([g[1] for g in grads]), GSTRIDE,
+                      pa([raw[l:l + 1] for l in range(nl)]), ops._dt(inp.head[0][0]), ops._stream())
+    elif entry == "levels":
+        ops.fcos_loss_levels(0, inp.head, inp.gtb, inp.cnt, spec.FPN_STRIDES[:nl], SIZE_RANGES[:nl], spec.POS_RADIUS, spec.LOSS_GAMMA,
+                             spec.LOSS_ALPHA, None, sums, **mode)
+        ops.fcos_loss_levels(1, inp.head, inp.gtb, inp.cnt, spec.FPN_STRIDES[:nl], SIZE_RANGES[:nl], spec.POS_RADIUS, spec.LOSS_GAMMA,
+                             spec.LOSS_ALPHA, sc, sums, [g[0] for g in grads], [g[1] for g in grads],
+                             [raw[l:l + 1] for l in range(nl)], **mode)
+    else:
+        for phase in (0, 1):
+            for l, (cc, rg) in enumerate(inp.head):
+                lo, hi = SIZE_RANGES[l]
+                ops.fcos_loss_level(phase, cc, rg, inp.gtb, inp.cnt, spec.FPN_STRIDES[l], lo, hi, spec.POS_RADIUS, spec.LOSS_GAMMA,
+                                    spec.LOSS_ALPHA, sc[l] if phase else None, sums, grads[l][0] if phase else None,
+                                    grads[l][1] if phase else None, raw[l:l + 1] if phase else None, **mode)
+    losses = torch.empty(4, device="cuda", dtype=torch.float32)
+    _lib.call("osd_fcos_loss_finalize", ops._p(sums), ops._p(losses), inp.N, ops._stream())
+    torch.cuda.synchronize()
+    return losses.cpu(), sums[:5].cpu().double(), [(a.cpu(), b.cpu()) for a, b in grads], raw.cpu().double()
+
+
+def check_stored(got, ref, dtype, what):
+    res = lr.compare(got, ref, dtype)
+    assert res["ok"] and res["flips"] <= FLIP_CAP, (what, res)
+
+
+@pytest.mark.parametrize("dt", ["f32", "bf16"])
+@pytest.mark.parametrize("entry", ["level", "levels"])
+@pytest.mark.parametrize("name", CASES)
+@pytest.mark.parametrize("center_sample,loc_loss_type", flr.MODES)
+def test_losses_and_gradients_match_the_reference(center_sample, loc_loss_type, name, entry, dt):
+    f = gu.load("fcos_loss_modes.npz")
+    inp = Inputs(f, name, dt)
+    losses, sums, grads, raw = run_kernels(inp, entry, center_sample, loc_loss_type)
+    key = "%s.cs%d" % (name, center_sample)
+    mkey = "%s.%s" % (key, loc_loss_type)
+    want = f[mkey + ".losses_cuda_formula"]
+    print("\n%s %s %s %s: losses %s reference %s num_pos %d / %d" % (mkey, entry, dt, "", losses[:3].numpy(), want, int(losses[3]),
+                                                                   int(f[mkey + ".num_pos"])))
+    assert int(losses[3]) == int(f[mkey + ".num_pos"]) == int(f[key + ".labels"].sum())
+    np.testing.assert_allclose(losses[:3].numpy(), want, rtol=LOSS_RTOL[dt])
+    g_logit = inp.per_level(f[key + ".grad_logits_cuda_formula"], 1)
+    g_ctr = inp.per_level(f[mkey + ".grad_centerness"], 1)
+    g_reg = inp.per_level(f[mkey + ".grad_bbox_reg"], 4)
+    for l, (d_cc, d_x) in enumerate(grads):
+        check_stored(d_cc[..., 0:1], g_logit[l], DT[dt], "level %d logits" % l)
+        check_stored(d_cc[..., 1:2], g_ctr[l], DT[dt], "level %d centerness" % l)
+        ds = g_reg[l] * inp.flat_reg[l]                                       # chain through reg = exp(scale * x)
+        check_stored(d_x[..., :4], ds * SCALES[l], DT[dt], "level %d bbox conv output" % l)
+        assert float(d_cc[..., 2:].abs().max()) == 0.0 and float(d_x[..., 4:].abs().max()) == 0.0      # padding channels untouched
+        terms = ds.double() * inp.flat_reg[l].double().log()
+        assert abs(float(raw[l]) - float(terms.sum())) <= 1e-4 * float(terms.abs().sum()) + 1e-12, (l, float(raw[l]), float(terms.sum()))
+
+
+def test_old_entries_are_the_new_ones_in_the_default_mode():
+    """osd_fcos_loss_levels forwards to osd_fcos_loss_levels_opt(1, GIOU): equal up to the order of the atomic adds."""
+    f = gu.load("fcos_loss_modes.npz")
+    for dt in ("f32", "bf16"):
+        inp = Inputs(f, "quirks", dt)
+        l0, s0, g0, r0 = run_kernels(inp, "levels", True, "giou", old_symbol=True)
+        l1, s1, g1, r1 = run_kernels(inp, "levels", True, "giou")
+        assert int(l0[3]) == int(l1[3]) > 0
+        torch.testing.assert_close(l0, l1, rtol=1e-5, atol=0)
+        torch.testing.assert_close(s0, s1, rtol=1e-5, atol=0)
+        torch.testing.assert_close(r0, r1, rtol=1e-5, atol=1e-7)
+        for (a, b), (c, d) in zip(g0, g1):
+            check_stored(a, c.float(), DT[dt], "cls/ctr")
+            check_stored(b, d.float(), DT[dt], "reg")
+
+
+@pytest.mark.parametrize("dt", ["f32", "bf16"])
+@pytest.mark.parametrize("center_sample,loc_loss_type", [(False, "iou"), (True, "linear_iou")])
+def test_level_by_level_and_all_levels_entries_agree(center_sample, loc_loss_type, dt):
+    f = gu.load("fcos_loss_modes.npz")
+    inp = Inputs(f, "quirks", dt)
+    l0, s0, g0, r0 = run_kernels(inp, "level", center_sample, loc_loss_type)
+    l1, s1, g1, r1 = run_kernels(inp, "levels", center_sample, loc_loss_type)
+    assert int(l0[3]) == int(l1[3]) > 0
+    torch.testing.assert_close(l0, l1, rtol=1e-5, atol=0)
+    torch.testing.assert_close(s0, s1, rtol=1e-5, atol=0)
+    torch.testing.assert_close(r0, r1, rtol=1e-5, atol=1e-7)
+    for (a, b), (c, d) in zip(g0, g1):
+        check_stored(a, c.float(), DT[dt], "cls/ctr")
+        check_stored(b, d.float(), DT[dt], "reg")
+
+
+@pytest.mark.parametrize("dt", ["f32", "bf16"])
+@pytest.mark.parametrize("center_sample,loc_loss_type", [(False, "iou"), (False, "linear_iou"), (True, "iou")])
+def test_loss_sums_are_additive_over_images(center_sample, loc_loss_type, dt):
+    """{num_pos, sum_w, sum_focal, sum_w * loc_loss, sum_bce} of a batch are the sums of its images' runs (target assignment and
+    loss terms of an image do not see the other images), and the losses follow from them by fcos/loss.py:251-271."""
+    f = gu.load("fcos_loss_modes.npz")
+    inp = Inputs(f, "random", dt)
+    lb, sb, _, _ = run_kernels(inp, "levels", center_sample, loc_loss_type)
+    tot = torch.zeros(5, dtype=torch.float64)
+    for i in range(inp.N):
+        _, s, _, _ = run_kernels(Inputs(f, "random", dt, images=[i]), "levels", center_sample, loc_loss_type)
+        tot += s
+    assert int(sb[0]) == int(tot[0]) == int(f["random.cs%d.%s.num_pos" % (center_sample, loc_loss_type)])
+    torch.testing.assert_close(sb, tot, rtol=1e-5, atol=1e-6)
+    expect = torch.stack([tot[2] / (tot[0] + inp.N), tot[3] / tot[1], tot[4] / tot[0]])
+    torch.testing.assert_close(lb[:3].double(), expect, rtol=1e-5, atol=1e-7)
+
+
+@pytest.mark.parametrize("center_sample", [True, False])
+def test_image_without_boxes_is_all_background(center_sample):
+    """gt_count 0: label 0 everywhere in that image in both modes (the reference cannot run it with CENTER_SAMPLE off, so this is
+    held to the restatement), and no regression / centerness gradient there."""
+    f = gu.load("fcos_loss_modes.npz")
+    inp = Inputs(f, "random", "f32")
+    inp.cnt = torch.tensor([0] + [len(g) for g in inp.gts[1:]], dtype=torch.int32).cuda()
+    gts = [np.zeros((0, 4), np.float32)] + inp.gts[1:]
+    losses, _, grads, _ = run_kernels(inp, "levels", center_sample, "iou")
+    lv = [[lr.nchw(cc.cpu())[:, 0:1] for cc, _ in inp.head], [lr.nchw(rg.cpu()) for _, rg in inp.head],
+          [lr.nchw(cc.cpu())[:, 1:2] for cc, _ in inp.head]]
+    c, r, t, info = flr.fcos_loss(lv[0], lv[1], lv[2], gts, focal="cuda", center_sample=center_sample, loc_loss_type="iou")
+    assert int(losses[3]) == info["num_pos"] > 0
+    np.testing.assert_allclose(losses[:3].numpy(), [c.item(), r.item(), t.item()], rtol=1e-4)
+    for d_cc, d_x in grads:
+        assert float(d_x[0].abs().max()) == 0.0 and float(d_cc[0, ..., 1].abs().max()) == 0.0
+
+
+def _engine_and_inputs(dt, name="small", **kw):
+    from oneshotdet_amd import train
+    B, H, W, S, qh, qw = gu.CASES[name]
+    img, q = gu.case_inputs(name)
+    gts = synth.make_gt_boxes(B, H, W, seed=3, max_boxes=3)
+    eng = train.TrainEngine(synth.make_state_dict(spec.hot_path_shapes()), dtype=DT[dt], **kw)
+    G = max(len(g) for g in gts)
+    gtb = torch.zeros(B, G, 4)
+    for i, g in enumerate(gts):
+        gtb[i, :len(g)] = torch.from_numpy(g)
+    cnt = torch.tensor([len(g) for g in gts], dtype=torch.int32)
+    return eng, torch.from_numpy(img).cuda(), torch.from_numpy(q).cuda(), gtb.cuda(), cnt.cuda(), gts
+
+
+def _traced(fn):
+    from oneshotdet_amd import trace
+    trace.TRACE = []
+    try:
+        out = fn()
+        torch.cuda.synchronize()
+        return out, trace.TRACE
+    finally:
+        trace.TRACE = None
+
+
+def test_train_step_in_the_reference_default_mode():
+    """TrainEngine(center_sample=False, loc_loss_type="iou"), fp32: the step's losses are the restatement's on the engine's OWN head
+    outputs (rtol 1e-4), they are not the default mode's, and a few SGD steps reduce the loss."""
+    eng, img, q, gtb, cnt, gts = _engine_and_inputs("f32", center_sample=False, loc_loss_type="iou")
+    assert (eng.center_sample, eng.loc_loss_type) == (False, "iou")
+    losses, tr = _traced(lambda: eng.forward_backward(img, q, gtb, cnt).cpu())
+    rec = [r for kind, r in tr if kind == "fcos_loss"]
+    head = rec[0]["head_out"]
+    lv = [[lr.nchw(cc.cpu())[:, 0:1] for cc, _ in head], [lr.nchw(rg.cpu())[:, :4] for _, rg in head],
+          [lr.nchw(cc.cpu())[:, 1:2] for cc, _ in head]]
+    c, r, t, info = flr.fcos_loss(lv[0], lv[1], lv[2], gts, focal="cuda", center_sample=False, loc_loss_type="iou")
+    d = flr.fcos_loss(lv[0], lv[1], lv[2], gts, focal="cuda")
+    print("\nengine", losses.numpy(), "restatement", c.item(), r.item(), t.item(), info["num_pos"], "default mode", d[3]["num_pos"])
+    assert int(losses[3]) == info["num_pos"] > d[3]["num_pos"]
+    np.testing.assert_allclose(losses[:3].numpy(), [c.item(), r.item(), t.item()], rtol=1e-4)
+    assert abs(losses[1].item() - d[1].item()) > 1e-2 * d[1].item()
+    w0 = eng.flat_w.clone()
+    first = eng.train_step(img, q, gtb, cnt)[:3].sum().item()
+    for _ in range(5):
+        last = eng.train_step(img, q, gtb, cnt)[:3].sum().item()
+    assert not torch.equal(w0, eng.flat_w)
+    assert np.isfinite(last) and last < first
+
+
+def test_a_step_records_two_loss_launches_carrying_the_engines_mode():
+    """Launch trace: one launch per phase over all levels in every mode, with the options the engine was built with — (True, "giou")
+    for a default engine — and the same launches in the same order around them: no mode adds a launch to the step."""
+    kinds = {}
+    for mode in ((True, "giou"), (False, "iou"), (True, "linear_iou")):
+        kw = {} if mode == (True, "giou") else dict(center_sample=mode[0], loc_loss_type=mode[1])
+        eng, img, q, gtb, cnt, _ = _engine_and_inputs("bf16", **kw)
+        eng.forward_backward(img, q, gtb, cnt, with_proposals=False)      # warm-up: allocations, persistent buffers
+        torch.cuda.synchronize()
+        _, tr = _traced(lambda: eng.forward_backward(img, q, gtb, cnt, with_proposals=False))
+        rec = [r for kind, r in tr if kind == "fcos_loss"]
+        assert [r["phase"] for r in rec] == [0, 1], [r["phase"] for r in rec]
+        for r in rec:
+            assert (r["center_sample"], r["loc_loss_type"]) == mode
+            for key in ("head_out", "gt_boxes", "gt_count", "gamma", "alpha", "scale_devs", "sums", "d_cls_ctrs", "d_regs", "d_scale_raws"):
+                assert key in r, key
+        kinds[mode] = [kind for kind, _ in tr]
+    assert kinds[(False, "iou")] == kinds[(True, "giou")] == kinds[(True, "linear_iou")]
