@@ -180,7 +180,10 @@ int osd_pack_conv_weight_ex(const float* w, const float* scale, void* dst, int c
  * struct { int64 src_off, dst_off, scale_off; int32 cout, cin, r, s, rows, kpad, first_block, n_blocks; } (56 bytes),
  * src = flat fp32 masters in [cout][r][s][cin] order, scales = flat per-Cout factors (scale_off -1: none), dst = flat
  * packed buffer of `dtype`; block_entry[b] = table index served by workgroup b; dgrad != 0 writes the flipped /
- * transposed data-gradient form ([rows >= cin][r][s][kpad >= cout]). */
+ * transposed data-gradient form ([rows >= cin][r][s][kpad >= cout]).  Every element of an entry's [rows][r][s][kpad] block is
+ * written (padding: zero), nothing else.  Alignment: none required beyond that of the element types — an entry whose src_off is a
+ * multiple of 4 floats and whose dst_off and kpad are multiples of 16 bytes (4 fp32 / 8 bf16 elements; data-gradient form: kpad
+ * a multiple of 64) moves 16 bytes per lane, any other entry one value per lane with the same result. */
 int osd_pack_multi(const void* table, const int32_t* block_entry, int n_blocks, const float* src, const float* scales,
                    void* dst, int dgrad, int dtype, void* stream);
 int osd_pack_stem_weight(const float* w_oihw, const float* scale, void* dst, int cout, int w_rows, int dtype,
@@ -412,16 +415,24 @@ int osd_unpack_wgrad(const float* dw_packed, const float* scale, float* grad_oih
 /* db[c] (fp32, accumulated with atomics) += sum over m of dy[m][c] */
 int osd_bias_grad(const void* dy, float* db, int m, int c, int stride, int dtype, void* stream);
 /* data gradient of strided convs without the implicit-GEMM path (the two 3x3/2 convs P6/P7): forward-packed weights,
- * optional addend (same shape as dx) and ReLU mask */
+ * optional addend and ReLU mask (both dense, the shape of dx [n][h][w][cin]).  ORDER: dx = (mask > 0 ? gradient : 0) + addend — the mask
+ * is the ReLU backward of the conv's own input, the addend the other gradient branch of that tensor, which the mask does not
+ * touch (osd_scatter2x is the other way round).  d describes the FORWARD conv; read from it: dtype, n, h, w, cin, ho, wo, cout, r, s,
+ * stride_h, pad_h, out_stride (pixel stride of dy, >= cout).  Assumptions, not checked: stride_w == stride_h and pad_w == pad_h;
+ * the packed weight rows are [r][s][cin] with NO channel padding (cin_pad == cin: cin a multiple of 16 (fp32) / 64 (bf16) as
+ * osd_pack_conv_weight's callers pad it). */
 int osd_conv2d_dgrad_naive(const osd_conv_desc* d, const void* dy, const void* w_fwd_packed, const void* mask,
                            const void* addend, void* dx, void* stream);
 /* dst = mask>0 ? (zero-inserted src + addend) : 0, where zero-inserted src[n,2ho,2wo,:] = src[n,ho,wo,:] (dst, mask,
- * addend [n][h][w][c]; src [n][ho][wo][c]; mask, addend nullable) */
+ * addend [n][h][w][c]; src [n][ho][wo][c]; mask, addend nullable).  ORDER: the addend is added FIRST and the mask applies to the
+ * sum (both gradient branches pass through the same ReLU; osd_conv2d_dgrad_naive masks before it adds).  c a multiple of 16 bytes. */
 int osd_scatter2x(const void* src, const void* mask, const void* addend, void* dst, int n, int h, int w, int ho, int wo,
                   int c, int dtype, void* stream);
 /* out = (a + b) * (mask > 0); b and mask nullable */
 int osd_add_mask(const void* a, const void* b, const void* mask, void* out, int64_t numel, int dtype, void* stream);
-/* top[n,y,x,:] = prev[n,y,x,:] + sum_{2x2} inner[n,2y+i,2x+j,:]  (backward of the FPN nearest-2x top-down add; prev nullable) */
+/* top[n,y,x,:] = prev[n,y,x,:] + sum_{2x2} inner[n,2y+i,2x+j,:]  (backward of the FPN nearest-2x top-down add; prev nullable).
+ * h, w: the size of top / prev; inner is read as EXACTLY [n][2h][2w][c] (row pitch 2w pixels): a map of odd height or width has no
+ * such top and must not be passed with a halved size.  c a multiple of 16 bytes. */
 int osd_upsample2x_bwd(const void* inner, const void* prev, void* top, int n, int h, int w, int c, int dtype, void* stream);
 /* dq[n][c] = sum_p g[n,p,c] * feat[n,p,c] (correlation backward w.r.t. the pooled query; d_feat = osd_correlate_fwd(g, q)) */
 int osd_correlate_bwd_query(const void* g, const void* feat, float* dq, int n, int hw, int c, int dtype, void* stream);
@@ -451,9 +462,10 @@ int osd_cast_f32(const float* src, void* dst, int64_t numel, int dtype, void* st
 int osd_grad_wire_cast(const void* src, void* dst, int64_t numel, int to_wire, void* stream);
 /* SGD with momentum over the flat fp32 master / gradient / momentum buffers in ONE launch (the reference uses
  * torch.optim.SGD with per-parameter groups, solver/build.py:8-26; same update rule: g += wd*p; buf = momentum*buf + g
- * (buf = g on the first step); p -= lr*lr_mult*buf).  table: device array of
+ * (buf = g on the first step); p -= lr*lr_mult*buf; each of the three steps is ONE fused multiply-add in fp32, for every element
+ * alike, so a tensor's result does not depend on its offset, its size or the entry point).  table: device array of
  * struct { int64 off, numel; float lr_mult, wd; int32 first_block, n_blocks; } (32 bytes); block_entry[b] = entry of
- * workgroup b. */
+ * workgroup b.  Elements outside the table's entries are neither read nor written; momentum_buf is not read on the first step. */
 int osd_sgd_momentum_multi(const void* table, const int32_t* block_entry, int n_blocks, float* params,
                            const float* grads, float* momentum_buf, float lr, float momentum, int first_step,
                            void* stream);
@@ -463,8 +475,9 @@ int osd_sgd_momentum_multi(const void* table, const int32_t* block_entry, int n_
  * osd_sgd_momentum_multi + the forward half of the per-step repack (solver/build.py:8-26 has no counterpart for the latter: the
  * reference's convs read the fp32 parameters directly).  table: device array of struct { int64 off, numel; float lr_mult, wd;
  * int32 first_block, n_blocks; int64 dst_off (elements into `packed`; -1: update only), scale_off (floats into `scales`; -1:
- * none); int32 cin, rs, kpad, pad; } (64 bytes).  Tensors that start on a 16-byte boundary (and, packed, have cin % 4 == 0) take 16 bytes
- * per lane, the others one value per lane.  zero_grads != 0: the gradients are consumed — every element read is overwritten with
+ * none); int32 cin, rs, kpad, pad; } (64 bytes).  Tensors that start on a 16-byte boundary (off % 4 == 0; and, packed, have cin, kpad
+ * and dst_off all multiples of 4, so that a group of four lies in one tap's channel run and is stored as one value) take 16 bytes
+ * per lane, the others one value per lane with the same result: no alignment is required of the caller.  zero_grads != 0: the gradients are consumed — every element read is overwritten with
  * zero (optimizer.zero_grad() of engine/trainer.py:89 folded into the update: the weight-gradient kernels accumulate). */
 int osd_sgd_momentum_pack_multi(const void* table, const int32_t* block_entry, int n_blocks, float* params,
                                 float* grads, float* momentum_buf, const float* scales, void* packed, int dtype,

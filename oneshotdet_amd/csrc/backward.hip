@@ -80,7 +80,9 @@ __global__ void __launch_bounds__(256) pack_multi_kernel(const PackEntry* __rest
   const float* sc = e.scale_off >= 0 ? scales + e.scale_off : nullptr;
   T* out = dst + e.dst_off;
   constexpr int EP = 16 / (int)sizeof(T);     // elements of one 16-byte output chunk
-  if (!dgrad && e.cin % EP == 0 && e.kpad % EP == 0 && (e.src_off & 3) == 0) {
+  // (the 16-byte paths need 16-byte aligned loads AND stores: src_off in fours, dst_off / kpad in whole chunks; any other entry takes
+  // the one-value-per-lane path of its form)
+  if (!dgrad && e.cin % EP == 0 && e.kpad % EP == 0 && (e.src_off & 3) == 0 && e.dst_off % EP == 0) {
     // forward form, 16 bytes out per lane: a chunk lies entirely inside or entirely outside the real channels
     const int kch = e.kpad / EP;
     const int total = e.rows * e.R * e.S * kch;
@@ -130,7 +132,7 @@ __global__ void __launch_bounds__(256) pack_multi_kernel(const PackEntry* __rest
   }
   // data-gradient form [row = ci][r'][s'][k = co] with flipped taps: a transpose of the master per tap through LDS.
   // 64 x 64 tiles: 16-byte loads along ci, 16-byte stores along co
-  if (e.cin % 4 == 0 && e.kpad % 64 == 0 && (e.src_off & 3) == 0) {
+  if (e.cin % 4 == 0 && e.kpad % 64 == 0 && (e.src_off & 3) == 0 && e.dst_off % EP == 0) {
     __shared__ float big[64][65];
     const int tci = (e.rows + 63) / 64, tco = e.kpad / 64;
     const int ntiles = e.R * e.S * tci * tco;
@@ -211,6 +213,15 @@ struct SgdEntry {
   int first_block, n_blocks;
 };
 
+// One parameter's update: three fused multiply-adds, written out so that every path of both kernels below (16 bytes per lane, one
+// value per lane, tail) rounds alike — left to the compiler's contraction, two lanes of a group of four came out fused and two did
+// not, and a tensor's result depended on which path its alignment selected.
+__device__ __forceinline__ float sgd_update(float w, float g, float b, float wd, float momentum, float step, int first, float& m) {
+  const float d = __builtin_fmaf(wd, w, g);
+  m = first ? d : __builtin_fmaf(momentum, b, d);
+  return __builtin_fmaf(-step, m, w);
+}
+
 __global__ void __launch_bounds__(256) sgd_multi_kernel(const SgdEntry* __restrict__ table, const int* __restrict__ block_entry,
                                                         float* __restrict__ p, const float* __restrict__ g,
                                                         float* __restrict__ buf, float lr, float momentum, int first) {
@@ -225,28 +236,21 @@ __global__ void __launch_bounds__(256) sgd_multi_kernel(const SgdEntry* __restri
   f32x4* b4 = reinterpret_cast<f32x4*>(buf + e.off);
   for (long long i = tid; i < n4; i += stride) {
     const f32x4 w = p4[i], gr = g4[i];
-    f32x4 m;
-    if (first) {
+    f32x4 bb = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (!first) bb = b4[i];
+    f32x4 m, o;
 #pragma unroll
-      for (int k = 0; k < 4; ++k) m[k] = gr[k] + e.wd * w[k];
-    } else {
-      const f32x4 bb = b4[i];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) m[k] = momentum * bb[k] + (gr[k] + e.wd * w[k]);
-    }
-    f32x4 o;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) o[k] = w[k] - step * m[k];
+    for (int k = 0; k < 4; ++k) { float mk; o[k] = sgd_update(w[k], gr[k], bb[k], e.wd, momentum, step, first, mk); m[k] = mk; }
     b4[i] = m;
     p4[i] = o;
   }
   for (long long i = n4 * 4 + tid; i < e.numel; i += stride) {
     const long long k = e.off + i;
     const float w = p[k];
-    const float d = g[k] + e.wd * w;
-    const float m = first ? d : momentum * buf[k] + d;
+    float m;
+    const float o = sgd_update(w, g[k], first ? 0.f : buf[k], e.wd, momentum, step, first, m);
     buf[k] = m;
-    p[k] = w - step * m;
+    p[k] = o;
   }
 }
 
@@ -281,7 +285,8 @@ __global__ void __launch_bounds__(256) sgd_pack_multi_kernel(const SgdPackEntry*
   const bool pack = e.dst_off >= 0;
   // four values per thread where the tensor starts on a 16-byte boundary (and, packed, a group of four stays inside one tap's
   // channel run); otherwise — the 2- and 4-row prediction convs behind an odd-sized bias — one value per thread
-  const long long n4 = ((e.off & 3) == 0 && (!pack || (e.cin & 3) == 0)) ? (e.numel >> 2) : 0;
+  // (and the packed group of four is stored as one 8- / 16-byte value: dst_off and kpad in fours as well)
+  const long long n4 = ((e.off & 3) == 0 && (!pack || ((e.cin & 3) == 0 && (e.kpad & 3) == 0 && (e.dst_off & 3) == 0))) ? (e.numel >> 2) : 0;
   f32x4* p4 = reinterpret_cast<f32x4*>(p + e.off);
   f32x4* g4 = reinterpret_cast<f32x4*>(g + e.off);
   f32x4* b4 = reinterpret_cast<f32x4*>(buf + e.off);
@@ -290,18 +295,11 @@ __global__ void __launch_bounds__(256) sgd_pack_multi_kernel(const SgdPackEntry*
   const long long row4 = (long long)e.rs * cin4;            // groups of four per output row (co)
   for (long long i = tid; i < n4; i += stride) {
     const f32x4 w = p4[i], gr = g4[i];
-    f32x4 m;
-    if (first) {
+    f32x4 bb = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (!first) bb = b4[i];
+    f32x4 m, o;
 #pragma unroll
-      for (int k = 0; k < 4; ++k) m[k] = gr[k] + e.wd * w[k];
-    } else {
-      const f32x4 bb = b4[i];
-#pragma unroll
-      for (int k = 0; k < 4; ++k) m[k] = momentum * bb[k] + (gr[k] + e.wd * w[k]);
-    }
-    f32x4 o;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) o[k] = w[k] - step * m[k];
+    for (int k = 0; k < 4; ++k) { float mk; o[k] = sgd_update(w[k], gr[k], bb[k], e.wd, momentum, step, first, mk); m[k] = mk; }
     b4[i] = m;
     p4[i] = o;
     if (zero_grads) g4[i] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -325,9 +323,8 @@ __global__ void __launch_bounds__(256) sgd_pack_multi_kernel(const SgdPackEntry*
   for (long long i = n4 * 4 + tid; i < e.numel; i += stride) {
     const long long k = e.off + i;
     const float w = p[k];
-    const float d = g[k] + e.wd * w;
-    const float m = first ? d : momentum * buf[k] + d;
-    const float o = w - step * m;
+    float m;
+    const float o = sgd_update(w, g[k], first ? 0.f : buf[k], e.wd, momentum, step, first, m);
     buf[k] = m;
     p[k] = o;
     if (zero_grads) g[k] = 0.f;

@@ -996,6 +996,18 @@ def bias_grad(dy, db, c):
     _lib.call("osd_bias_grad", _p(dy), _p(db), n * h * w, c, stride, _dt(dy), _stream())
 
 
+def unpack_wgrad(dw_packed, scale=None, out=None, accumulate=False):
+    """packed fp32 dW [cout][r][s][cin] -> the OIHW gradient (x the folded FrozenBN scale), written or added to `out`."""
+    _chk_dev(dw_packed, scale, out)
+    cout, r, s, cin = dw_packed.shape
+    if out is None:
+        if accumulate:
+            raise ValueError("unpack_wgrad: accumulate needs the tensor to add to")
+        out = torch.empty((cout, cin, r, s), device=dw_packed.device, dtype=torch.float32)
+    _lib.call("osd_unpack_wgrad", _p(dw_packed), _p(scale), _p(out), cout, cin, r, s, int(bool(accumulate)), _stream())
+    return out
+
+
 def conv2d_dgrad_naive(dy, w_fwd_packed, x_shape, r, s, stride, pad, cout, mask=None, addend=None):
     d = _conv_desc(x_shape, _dt(dy), cout, r, s, stride, pad, dy.shape[-1])
     dx = torch.empty(x_shape, device=dy.device, dtype=dy.dtype)
@@ -1022,6 +1034,8 @@ def add_mask(a, b=None, mask=None, out=None):
 
 def upsample2x_bwd(inner, prev=None):
     n, h2, w2, c = inner.shape
+    if h2 % 2 or w2 % 2:      # the kernel addresses `inner` as [n][2h][2w][c]: a halved odd size would read the wrong pixels
+        raise ValueError("upsample2x_bwd: the gradient map must have even height and width, got %d x %d" % (h2, w2))
     top = torch.empty((n, h2 // 2, w2 // 2, c), device=inner.device, dtype=inner.dtype)
     _lib.call("osd_upsample2x_bwd", _p(inner), _p(prev), _p(top), n, h2 // 2, w2 // 2, c, _dt(inner), _stream())
     _rec("upsample2x_bwd", inner=inner, prev=prev, out=top)

@@ -87,7 +87,18 @@ def run_kernels(inp, entry, center_sample, loc_loss_type, old_symbol=False):
               torch.zeros(cc.shape[:3] + (GSTRIDE,), device="cuda", dtype=cc.dtype)) for cc, _ in inp.head]
     sc = [inp.scales[l:l + 1] for l in range(nl)]
     mode = dict(center_sample=center_sample, loc_loss_type=loc_loss_type)
-    if old_symbol:
+    if old_symbol and entry == "level":
+        assert (center_sample, loc_loss_type) == (True, "giou")
+        for phase in (0, 1):
+            for l, (cc, rg) in enumerate(inp.head):
+                lo, hi = SIZE_RANGES[l]
+                n, h, w, _ = cc.shape
+                _lib.call("osd_fcos_loss_level", phase, ops._p(cc), ops._p(rg), ops._p(inp.gtb), ops._p(inp.cnt), inp.gtb.shape[1], n, h, w,
+                          spec.FPN_STRIDES[l], float(lo), float(hi), float(spec.POS_RADIUS), float(spec.LOSS_GAMMA), float(spec.LOSS_ALPHA),
+                          ops._p(sc[l]) if phase else None, ops._p(sums), ops._p(grads[l][0]) if phase else None,
+                          ops._p(grads[l][1]) if phase else None, GSTRIDE, ops._p(raw[l:l + 1]) if phase else None, ops._dt(cc),
+                          ops._stream())
+    elif old_symbol:
         assert (center_sample, loc_loss_type) == (True, "giou")
         k, n = nl, inp.N
         hs = (C.c_int32 * k)(*[h for h, _ in inp.hw])
@@ -154,19 +165,21 @@ def test_losses_and_gradients_match_the_reference(center_sample, loc_loss_type, 
 
 
 def test_old_entries_are_the_new_ones_in_the_default_mode():
-    """osd_fcos_loss_levels forwards to osd_fcos_loss_levels_opt(1, GIOU): equal up to the order of the atomic adds."""
+    """osd_fcos_loss_levels forwards to osd_fcos_loss_levels_opt(1, GIOU), osd_fcos_loss_level to osd_fcos_loss_level_opt(1, GIOU): equal
+    up to the order of the atomic adds."""
     f = gu.load("fcos_loss_modes.npz")
     for dt in ("f32", "bf16"):
         inp = Inputs(f, "quirks", dt)
-        l0, s0, g0, r0 = run_kernels(inp, "levels", True, "giou", old_symbol=True)
-        l1, s1, g1, r1 = run_kernels(inp, "levels", True, "giou")
-        assert int(l0[3]) == int(l1[3]) > 0
-        torch.testing.assert_close(l0, l1, rtol=1e-5, atol=0)
-        torch.testing.assert_close(s0, s1, rtol=1e-5, atol=0)
-        torch.testing.assert_close(r0, r1, rtol=1e-5, atol=1e-7)
-        for (a, b), (c, d) in zip(g0, g1):
-            check_stored(a, c.float(), DT[dt], "cls/ctr")
-            check_stored(b, d.float(), DT[dt], "reg")
+        for entry in ("levels", "level"):
+            l0, s0, g0, r0 = run_kernels(inp, entry, True, "giou", old_symbol=True)
+            l1, s1, g1, r1 = run_kernels(inp, entry, True, "giou")
+            assert int(l0[3]) == int(l1[3]) > 0
+            torch.testing.assert_close(l0, l1, rtol=1e-5, atol=0)
+            torch.testing.assert_close(s0, s1, rtol=1e-5, atol=0)
+            torch.testing.assert_close(r0, r1, rtol=1e-5, atol=1e-7)
+            for (a, b), (c, d) in zip(g0, g1):
+                check_stored(a, c.float(), DT[dt], "cls/ctr")
+                check_stored(b, d.float(), DT[dt], "reg")
 
 
 @pytest.mark.parametrize("dt", ["f32", "bf16"])

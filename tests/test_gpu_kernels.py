@@ -371,6 +371,23 @@ def test_empty_inputs_are_noops():
     assert y.shape == (0, 4, 4, 256)
     r = o.roi_align(torch.zeros(1, 4, 4, 8, device="cuda"), torch.zeros(0, 5, device="cuda"), 0.5, 1, 1, 2)
     assert r.shape == (0, 1, 1, 8)
+    # the launchers with an early return (numel == 0, n_blocks == 0, m == 0, no locations): OK, and nothing is written
+    from oneshotdet_amd import _lib
+    buf = torch.full((64,), 7.0, device="cuda")
+    p, st = buf.data_ptr(), o._stream()
+    _lib.call("osd_add_mask", p, p, p, p, 0, 0, st)
+    _lib.call("osd_pack_multi", p, p, 0, p, p, p, 0, 0, st)
+    _lib.call("osd_pack_multi", p, p, 0, p, p, p, 1, 1, st)
+    _lib.call("osd_sgd_momentum_multi", p, p, 0, p, p, p, 0.1, 0.9, 1, st)
+    _lib.call("osd_sgd_momentum_pack_multi", p, p, 0, p, p, p, p, p, 1, 0.1, 0.9, 0, 1, st)
+    _lib.call("osd_bias_grad", p, p, 0, 8, 8, 0, st)
+    _lib.call("osd_bias_grad", p, p, 4, 0, 8, 1, st)
+    _lib.call("osd_fcos_score_decode", p, p, p, p, 0, 2, 2, 4, 4, 8, 0, 4, 16.0, 16.0, 0, st)
+    _lib.call("osd_fcos_score_decode_sizes", p, p, p, p, 1, 0, 2, 4, 4, 8, 0, 4, 16.0, 16.0, p, 1, st)
+    _lib.call("osd_level_topk", p, p, 1, 16, 3, 0, 5, st)
+    _lib.call("osd_level_topk", p, p, 0, 16, 3, 4, 5, st)
+    torch.cuda.synchronize()
+    assert bool((buf == 7.0).all())
 
 
 def test_sigmoid_focal_loss_fwd_bwd():
