@@ -6,6 +6,7 @@ RyanXLi/OneshotDet drive it (both stages, SGD with the reference's parameter gro
                              [--no-supp-roialign]       # the query pyramid pooled by global average (SUPP_ROIALIGN False)
                              [--no-center-sample]       # positives inside the whole box (FCOS.CENTER_SAMPLE False)
                              [--loc-loss-type giou|iou|linear_iou]      # the regression loss (FCOS.LOC_LOSS_TYPE)
+                             [--box-cls-loss ce_loss|focal_loss|mse_loss]   # the second stage's classification loss
     python examples/train.py --no-center-sample --loc-loss-type iou ...    # the loss of the reference's defaults (defaults.py:309-311)
     python examples/train.py --shared-backbone --no-supp-roialign ...      # the 0930 model (configs/fcos/0930fixed_thres.yaml)
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 examples/train.py ...      # one rank per GPU
@@ -63,6 +64,8 @@ def main():
     ap.add_argument("--no-center-sample", action="store_true", help="positives inside the whole box (FCOS.CENTER_SAMPLE False)")
     ap.add_argument("--loc-loss-type", default=spec.LOC_LOSS_TYPE, choices=list(spec.LOC_LOSS_TYPES),
                     help="regression loss (FCOS.LOC_LOSS_TYPE): 1 - giou, -log(iou) or 1 - iou")
+    ap.add_argument("--box-cls-loss", default=spec.BOX_CLS_LOSS, choices=list(spec.BOX_CLS_LOSSES),
+                    help="second-stage classification loss (FEW_SHOT.SECOND_STAGE_CLS_LOSS); the sigmoid losses have one class logit")
     args = ap.parse_args()
     siamese = not args.shared_backbone
     roialign = not args.no_supp_roialign
@@ -70,17 +73,19 @@ def main():
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
     dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float32
-    shapes = spec.hot_path_shapes(siamese) if args.first_stage_only else spec.full_model_shapes(siamese)
+    shapes = spec.hot_path_shapes(siamese) if args.first_stage_only else spec.full_model_shapes(siamese, box_cls_loss=args.box_cls_loss)
 
     def make_engine(sd):
         return train.TrainEngine(sd, dtype=dtype, lr=0.0005, second_stage=not args.first_stage_only, siamese_backbone=siamese,
-                                 supp_roialign=roialign, center_sample=center_sample, loc_loss_type=args.loc_loss_type)
+                                 supp_roialign=roialign, center_sample=center_sample, loc_loss_type=args.loc_loss_type,
+                                 box_cls_loss=args.box_cls_loss)
     start = 0
     last = os.path.join(args.out, "last_checkpoint")
     if args.resume and os.path.exists(last):
         eng, start = checkpoint.resume_training(open(last).read().strip(), make_engine, siamese_backbone=siamese,
                                                 supp_roialign=roialign, center_sample=center_sample,
-                                                loc_loss_type=args.loc_loss_type)
+                                                loc_loss_type=args.loc_loss_type,
+                                                box_cls_loss=None if args.first_stage_only else args.box_cls_loss)
         print("resumed at iteration", start)
     else:
         eng = make_engine(synth.make_state_dict(shapes))      # or checkpoint.load_checkpoint / load_c2_resnet, see detect.py

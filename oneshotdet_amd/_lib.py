@@ -128,6 +128,14 @@ SIGNATURES = {
     "osd_image_transform_batch": (_i, [_i, _p, _p, _p, _p, _p, _p, _i, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p]),
 }
 
+# include/oneshotdet_hip_box_modes.h: the second stage's classification-loss modes (a table of its own: SIGNATURES lists the main
+# header's functions and nothing else).  load() binds both tables, call() finds the entries of either.
+BOX_CLS_CE, BOX_CLS_FOCAL, BOX_CLS_MSE = 0, 1, 2
+SIGNATURES_BOX_MODES = {
+    "osd_box_loss_opt": (_i, [_p, _p, _p, _p, _i, _i, _i, _f, _f, _p, _p, _i, _i, _i, _f, _f, _p]),
+    "osd_box_decode_opt": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _f, _f, _p, _f, _i, _i, _p]),
+}
+
 _lib = None
 
 
@@ -146,7 +154,7 @@ def load():
                        "__graft_entry__.build(); there is no CPU/eager fallback" % LIB_PATH)
     import torch  # noqa: F401  (loads libamdhip64 first)
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
+    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_BOX_MODES.items()):
         fn = getattr(lib, name)   # AttributeError if the symbol is missing
         fn.restype = res
         fn.argtypes = args

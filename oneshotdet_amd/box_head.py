@@ -1,7 +1,8 @@
 """Second-stage few-shot ROI box head on MI355X, inference path.
 
 Mirrors ROIBoxHead.forward (modeling/roi_heads/box_head/box_head.py:81-259) for the config of record
-(SECOND_STAGE_METHOD 'concat', no negative support, 'ce_loss'):
+(SECOND_STAGE_METHOD 'concat', no negative support; SECOND_STAGE_CLS_LOSS 'ce_loss', or with box_cls_loss 'focal_loss' /
+'mse_loss': cls_score has ONE output and the score is its sigmoid, inference.py:61-69):
   feature_extractor = Pooler 7x7 over P3..P7 of the TARGET backbone (not the correlated maps: generalized_rcnn.py:317)
   supproi_pooling   = the same Pooler on one whole-image box per query (generalized_rcnn.py:257,290)
   cat(x, query) -> conv1x1 512->512, GN, LeakyReLU -> conv1x1 512->256, GN, LeakyReLU -> conv3x3 256->128, GN, LeakyReLU
@@ -22,7 +23,9 @@ from .ops import ACT_NONE, ACT_RELU, PackedConv
 class BoxHeadWeights(object):
     """Packed `roi_heads.box.*` (spec.box_head_shapes)."""
 
-    def __init__(self, sd, dtype, prefix="roi_heads.box."):
+    def __init__(self, sd, dtype, prefix="roi_heads.box.", box_cls_loss="ce_loss"):
+        self.box_cls_loss = spec.box_cls_loss_mode(box_cls_loss)
+        spec.check_box_cls_score(sd, self.box_cls_loss, prefix)      # a 1-row cls_score must never be read as two logits
         c = spec.FPN_OUT
         w0, b0 = sd[prefix + "compress_dim_conv.0.weight"], sd[prefix + "compress_dim_conv.0.bias"]
         self.conv0_x = ops.pack_conv(w0[:, :c].contiguous(), bias=None, dtype=dtype)          # ROI half, no bias
@@ -43,7 +46,17 @@ class BoxHeadWeights(object):
         self.fc7 = ops.pack_conv(sd[prefix + "fc7.weight"][:, :, None, None], bias=sd[prefix + "fc7.bias"], dtype=dtype)
         wp = torch.cat([sd[prefix + "predictor.cls_score.weight"], sd[prefix + "predictor.bbox_pred.weight"]], 0)
         bp = torch.cat([sd[prefix + "predictor.cls_score.bias"], sd[prefix + "predictor.bbox_pred.bias"]], 0)
-        self.pred = ops.pack_conv(wp[:, :, None, None].contiguous(), bias=bp, dtype=dtype)  # cols 0..1 cls, 2..9 deltas
+        self.pred = ops.pack_conv(wp[:, :, None, None].contiguous(), bias=bp, dtype=dtype)  # cols 0..L-1 cls (L = 2, or 1 in the sigmoid modes), then 8 deltas
+
+
+def check_shots(box_cls_loss, shots):
+    """Inference with several queries per image exists for 'ce_loss' only: in the one-logit modes the reference's arg-max over
+    shots builds a 4-column index ([M, 1] logits) for the 8 regression columns and raises IndexError (box_head.py:246-253).
+    Training is unaffected: it uses the first query only (box_head.py:123-203)."""
+    if shots > 1 and box_cls_loss != "ce_loss":
+        raise ValueError("box_cls_loss=%r with %d shots: the reference's arg-max over shots indexes the 8 regression columns of a "
+                         "one-logit predictor with a 4-column index and raises IndexError (box_head.py:246-253); the second stage "
+                         "detects with one shot in this mode" % (box_cls_loss, shots))
 
 
 def query_level(qh, qw):
@@ -74,6 +87,7 @@ def run_box_head(bw, feats, qfeats, q_size, boxes, counts, img_h, img_w, shots=1
     Returns dict(boxes [N,K,4], scores [N,K] descending, counts [N]) (+ raw logits / deltas / pooled maps)."""
     n, r, _ = boxes.shape
     dtype = feats[0].dtype
+    check_shots(bw.box_cls_loss, shots)                                                # nothing has been launched yet
     q = run_query_roi(qfeats, q_size, dtype)                                           # [N*S,7,7,C]
     assert q.shape[0] == n * shots
     q_half = ops.conv2d(q, bw.conv0_q)                                                 # [N*S,7,7,512]  W_q q + b
@@ -92,7 +106,7 @@ def run_box_head(bw, feats, qfeats, q_size, boxes, counts, img_h, img_w, shots=1
         t = ops.conv2d(t, bw.fc7, act=ACT_RELU)
         ops.conv2d(t, bw.pred, act=ACT_NONE, out=preds[s].view(n * r, 1, 1, -1))
     dec = ops.box_decode(preds, boxes, counts, spec.BOX_REG_WEIGHTS, img_h, img_w, spec.BOX_SCORE_THRESH, want_raw=want_raw,
-                         img_hw=img_hw)
+                         img_hw=img_hw, cls_loss=bw.box_cls_loss)
     scores, dboxes = dec[0], dec[1]
     bs, ss, _, cnt = ops.rank_sort_gather(scores, dboxes, r)
     keep = min(spec.BOX_DETECTIONS_PER_IMG, r)

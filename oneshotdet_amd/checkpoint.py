@@ -13,6 +13,9 @@ siamese_backbone (FEW_SHOT.SIAMESE_BACKBONE): True = the two-backbone model (a s
 supp_roialign (FEW_SHOT.SUPP_ROIALIGN) changes no key: the query pooling has no weights, so loading is the same in both modes;
 training checkpoints record it, and `resume_training` refuses to continue a run in the other mode.  The same holds for the loss
 options center_sample / loc_loss_type (FCOS.CENTER_SAMPLE / FCOS.LOC_LOSS_TYPE): the loss has no parameters.
+box_cls_loss (FEW_SHOT.SECOND_STAGE_CLS_LOSS) changes a SHAPE: `roi_heads.box.predictor.cls_score.*` has 2 rows for 'ce_loss' and
+1 for 'focal_loss' / 'mse_loss'.  Loading checks the shapes of the mode it is given; the two one-row modes share their shapes, so
+training checkpoints record the mode and `resume_training` refuses to continue a run on the other loss.
 """
 import os
 import pickle
@@ -72,16 +75,17 @@ def has_query_backbone(path_or_sd):
     return any(k.startswith("supp_backbone.") for k in strip_prefix_if_present(sd))
 
 
-def load_checkpoint(path, second_stage=None, defaults=None, siamese_backbone=True):
+def load_checkpoint(path, second_stage=None, defaults=None, siamese_backbone=True, box_cls_loss="ce_loss"):
     """Read a reference `.pth` (or a bare state_dict file) -> (state_dict under the reference's key names, extras).
     second_stage: True = require roi_heads.box.*, False = first stage only, None = take it when present.
     defaults: values for keys the file lacks (utils/checkpoint.py:107-115 keeps the model's own initialisation for
     FEW_SHOT.UNLOAD_KEYWORD modules); without it a missing key is an error.
-    siamese_backbone=False: read the shared-backbone model's keys only (any `supp_backbone.*` in the file is ignored)."""
+    siamese_backbone=False: read the shared-backbone model's keys only (any `supp_backbone.*` in the file is ignored).
+    box_cls_loss: the second stage's classification loss the file was trained with (the shape of its cls_score)."""
     data = _read(path)
     loaded = data.pop("model")
     shapes = spec.hot_path_shapes(siamese_backbone)
-    box = spec.box_head_shapes()
+    box = spec.box_head_shapes(box_cls_loss=box_cls_loss)
     probe = strip_prefix_if_present(loaded)
     has_box = any(k.endswith("box.fc6.weight") for k in probe)
     if second_stage or (second_stage is None and has_box):
@@ -113,12 +117,14 @@ def save_training_checkpoint(path, engine, iteration, tag_last=True):
     """utils/checkpoint.py:33-50 as the trainer calls it (engine/trainer.py:111-119): model + optimizer + iteration.
     `optimizer` holds TrainEngine.optimizer_state_dict() (momentum buffers under reference names, steps taken, lr);
     `siamese_backbone` the engine's mode (a shared engine writes no `supp_backbone.*`); `supp_roialign` its query pooling (the
-    only record of it: the pooling has no weights); `center_sample` / `loc_loss_type` the FCOS loss it trained with (likewise)."""
+    only record of it: the pooling has no weights); `center_sample` / `loc_loss_type` the FCOS loss it trained with (likewise);
+    `box_cls_loss` the second stage's classification loss (the two one-logit losses have the same shapes)."""
     return save_checkpoint(path, engine.state_dict(), tag_last=tag_last, optimizer=engine.optimizer_state_dict(),
                            iteration=int(iteration), siamese_backbone=bool(getattr(engine, "siamese_backbone", True)),
                            supp_roialign=bool(getattr(engine, "supp_roialign", True)),
                            center_sample=bool(getattr(engine, "center_sample", spec.CENTER_SAMPLE)),
-                           loc_loss_type=str(getattr(engine, "loc_loss_type", spec.LOC_LOSS_TYPE)))
+                           loc_loss_type=str(getattr(engine, "loc_loss_type", spec.LOC_LOSS_TYPE)),
+                           box_cls_loss=str(getattr(engine, "box_cls_loss", spec.BOX_CLS_LOSS)))
 
 
 def _loss_name(mode):
@@ -126,7 +132,8 @@ def _loss_name(mode):
         ("centre-sampled " if mode[0] else "whole-box ") + mode[1], mode[0], mode[1])
 
 
-def resume_training(path, make_engine, siamese_backbone=None, supp_roialign=None, center_sample=None, loc_loss_type=None):
+def resume_training(path, make_engine, siamese_backbone=None, supp_roialign=None, center_sample=None, loc_loss_type=None,
+                    box_cls_loss=None):
     """Load a checkpoint written by save_training_checkpoint: make_engine(state_dict) -> TrainEngine; its momentum and
     step count are restored.  Returns (engine, iteration).  The file's mode (recorded by save_training_checkpoint; for
     older files: whether it holds `supp_backbone.*`) must be the engine's: a resumed run never ties or unties weights
@@ -134,8 +141,14 @@ def resume_training(path, make_engine, siamese_backbone=None, supp_roialign=None
     for the query pooling: supp_roialign is the caller's expectation, the file's record (True when it has none, the
     files written before the option existed) must match it and the engine's.  And for the FCOS loss: center_sample /
     loc_loss_type are the caller's expectations (None: whatever the file holds), a file without the fields was trained with
-    (True, "giou"), the only loss there was."""
+    (True, "giou"), the only loss there was.  And for the second stage's classification loss: box_cls_loss is the caller's
+    expectation (None: whatever the file holds), a file without the field was trained with "ce_loss"."""
     data = _read(path)
+    box = data.get("box_cls_loss")
+    box = spec.BOX_CLS_LOSS if box is None else spec.box_cls_loss_mode(str(box))
+    if box_cls_loss is not None and spec.box_cls_loss_mode(box_cls_loss) != box:
+        raise ValueError("%s was trained with box_cls_loss=%r; resuming it with box_cls_loss=%r would continue the run on another "
+                         "objective: build the engine with box_cls_loss=%r" % (path, box, box_cls_loss, box))
     loss = (data.get("center_sample"), data.get("loc_loss_type"))
     loss = (spec.CENTER_SAMPLE if loss[0] is None else bool(loss[0]), spec.LOC_LOSS_TYPE if loss[1] is None else str(loss[1]))
     want = spec.loss_mode(loss[0] if center_sample is None else center_sample, loss[1] if loc_loss_type is None else loc_loss_type)
@@ -154,8 +167,12 @@ def resume_training(path, make_engine, siamese_backbone=None, supp_roialign=None
                          "load_checkpoint(..., siamese_backbone=%r) into a fresh run instead"
                          % (path, _MODE[mode], _MODE[bool(siamese_backbone)], "untie" if siamese_backbone else "tie",
                             bool(siamese_backbone)))
-    sd, extras = load_checkpoint(path, siamese_backbone=mode)
+    sd, extras = load_checkpoint(path, siamese_backbone=mode, box_cls_loss=box)
     eng = make_engine(sd)
+    built_box = str(getattr(eng, "box_cls_loss", spec.BOX_CLS_LOSS))
+    if built_box != box:
+        raise ValueError("%s was trained with box_cls_loss=%r but make_engine built an engine with box_cls_loss=%r"
+                         % (path, box, built_box))
     if bool(getattr(eng, "siamese_backbone", True)) != mode:
         raise ValueError("%s holds a %s model but make_engine built a %s engine (siamese_backbone=%r)"
                          % (path, _MODE[mode], _MODE[not mode], not mode))
@@ -211,7 +228,7 @@ def translate_c2_resnet_name(name):
     return None if leaf is None else "layer%d.%d.%s.%s" % (stage - 1, block, conv, leaf)
 
 
-def load_c2_resnet(path, defaults, second_stage=None, siamese_backbone=True):
+def load_c2_resnet(path, defaults, second_stage=None, siamese_backbone=True, box_cls_loss="ce_loss"):
     """A Detectron ResNet `.pkl` (dict of numpy blobs, optionally under "blobs"; pickled by Python 2: latin1) -> a full
     state_dict: the ResNet bodies of BOTH backbones come from the file, every other entry (FrozenBN running statistics —
     AffineChannel has none —, FPN, FCOS head, second stage) from `defaults`, as `DetectronCheckpointer.load` leaves the
@@ -226,7 +243,7 @@ def load_c2_resnet(path, defaults, second_stage=None, siamese_backbone=True):
             loaded[name] = torch.as_tensor(blobs[k])
     shapes = spec.hot_path_shapes(siamese_backbone)
     if second_stage or (second_stage is None and all(k in defaults for k in spec.box_head_shapes())):
-        shapes.update(spec.box_head_shapes())
+        shapes.update(spec.box_head_shapes(box_cls_loss=box_cls_loss))
     body = OrderedDict((k, v) for k, v in shapes.items() if ".body." in k and not k.endswith(("running_mean", "running_var")))
     sd, missing = align_state_dict(body, loaded)
     if missing:

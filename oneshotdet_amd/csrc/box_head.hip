@@ -5,6 +5,7 @@
 //                                                                    modeling/box_coder.py:50-95)
 // All HBM-bound.  The convolutions / fully connected layers of the head run on the implicit-GEMM kernels.
 #include "osd_common.h"
+#include "../../include/oneshotdet_hip_box_modes.h"
 
 namespace {
 
@@ -254,12 +255,16 @@ __global__ __launch_bounds__(256) void gn_act_rois_kernel(const T* __restrict__ 
 // the image (bounding_box.py:214-219).  pred: [shots][n*max_rois][pstride], columns 0..1 = logits, 2..9 = deltas.
 // scores: class-1 probability, or -1 (= dropped by osd_rank_sort_gather) for ROIs past counts[image] and for
 // probabilities that do not exceed `score_thresh` (inference.py:136).
-template <typename T>
-__global__ void box_decode_kernel(const T* __restrict__ pred, const float* __restrict__ rois, const int32_t* __restrict__ counts,
-                                  float* __restrict__ scores, float* __restrict__ boxes, float* __restrict__ logits_out,
-                                  float* __restrict__ reg_out, int n, int max_rois, int shots, int pstride, float wx,
-                                  float wy, float ww, float wh, float clip, float img_h, float img_w, float score_thresh,
-                                  const float* __restrict__ img_hw) {
+// MODE = FEW_SHOT.SECOND_STAGE_CLS_LOSS (include/oneshotdet_hip_box_modes.h).  The one-logit modes ('focal_loss', 'mse_loss'):
+// column 0 = the logit, 1..8 = deltas, score = sigmoid(logit) (inference.py:61-64,67-69); with several shots all 8 deltas come from
+// the shot with the largest logit (the reference itself fails there, box_head.py:246-253, and the Python layer refuses it).
+template <typename T, int MODE>
+__device__ __forceinline__ void box_decode_body(const T* __restrict__ pred, const float* __restrict__ rois,
+                                                const int32_t* __restrict__ counts, float* __restrict__ scores,
+                                                float* __restrict__ boxes, float* __restrict__ logits_out,
+                                                float* __restrict__ reg_out, int n, int max_rois, int shots, int pstride, float wx,
+                                                float wy, float ww, float wh, float clip, float img_h, float img_w,
+                                                float score_thresh, const float* __restrict__ img_hw) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n * max_rois) return;
   const int img = i / max_rois, ri = i % max_rois;
@@ -269,32 +274,46 @@ __global__ void box_decode_kernel(const T* __restrict__ pred, const float* __res
   }
   const size_t shot_stride = (size_t)n * max_rois * pstride;
   const T* p0 = pred + (size_t)i * pstride;
-  float l[2];
-  int arg[2];
-#pragma unroll
-  for (int j = 0; j < 2; ++j) {
-    l[j] = to_f32(p0[j]);
-    arg[j] = 0;
-    for (int s = 1; s < shots; ++s) {
-      const float v = to_f32(p0[s * shot_stride + j]);
-      if (v > l[j]) { l[j] = v; arg[j] = s; }
-    }
-  }
   float d[8];
+  float prob;
+  if constexpr (MODE == OSD_BOX_CLS_CE) {
+    float l[2];
+    int arg[2];
 #pragma unroll
-  for (int j = 0; j < 2; ++j)
+    for (int j = 0; j < 2; ++j) {
+      l[j] = to_f32(p0[j]);
+      arg[j] = 0;
+      for (int s = 1; s < shots; ++s) {
+        const float v = to_f32(p0[s * shot_stride + j]);
+        if (v > l[j]) { l[j] = v; arg[j] = s; }
+      }
+    }
 #pragma unroll
-    for (int k = 0; k < 4; ++k) d[4 * j + k] = to_f32(p0[arg[j] * shot_stride + 2 + 4 * j + k]);
-  if (logits_out) {
-    logits_out[2 * (size_t)i] = l[0];
-    logits_out[2 * (size_t)i + 1] = l[1];
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+      for (int k = 0; k < 4; ++k) d[4 * j + k] = to_f32(p0[arg[j] * shot_stride + 2 + 4 * j + k]);
+    if (logits_out) {
+      logits_out[2 * (size_t)i] = l[0];
+      logits_out[2 * (size_t)i + 1] = l[1];
+    }
+    const float m = fmaxf(l[0], l[1]);
+    const float e0 = expf(l[0] - m), e1 = expf(l[1] - m);
+    prob = e1 / (e0 + e1);
+  } else {
+    float l = to_f32(p0[0]);
+    int arg = 0;
+    for (int s = 1; s < shots; ++s) {
+      const float v = to_f32(p0[s * shot_stride]);
+      if (v > l) { l = v; arg = s; }
+    }
+#pragma unroll
+    for (int k = 0; k < 8; ++k) d[k] = to_f32(p0[arg * shot_stride + 1 + k]);
+    if (logits_out) logits_out[i] = l;
+    prob = 1.f / (1.f + expf(-l));
   }
   if (reg_out)
 #pragma unroll
     for (int k = 0; k < 8; ++k) reg_out[8 * (size_t)i + k] = d[k];
-  const float m = fmaxf(l[0], l[1]);
-  const float e0 = expf(l[0] - m), e1 = expf(l[1] - m);
-  const float prob = e1 / (e0 + e1);
   const float* b = rois + (size_t)i * 4;
   const float bw = b[2] - b[0] + 1.f, bh = b[3] - b[1] + 1.f;
   const float cx = b[0] + 0.5f * bw, cy = b[1] + 0.5f * bh;
@@ -312,6 +331,28 @@ __global__ void box_decode_kernel(const T* __restrict__ pred, const float* __res
   scores[i] = live ? prob : -1.f;
   float* o = boxes + (size_t)i * 4;
   o[0] = ox1; o[1] = oy1; o[2] = ox2; o[3] = oy2;
+}
+
+// 'ce_loss', the config of record: the launch osd_box_decode has always made
+template <typename T>
+__global__ void box_decode_kernel(const T* __restrict__ pred, const float* __restrict__ rois, const int32_t* __restrict__ counts,
+                                  float* __restrict__ scores, float* __restrict__ boxes, float* __restrict__ logits_out,
+                                  float* __restrict__ reg_out, int n, int max_rois, int shots, int pstride, float wx,
+                                  float wy, float ww, float wh, float clip, float img_h, float img_w, float score_thresh,
+                                  const float* __restrict__ img_hw) {
+  box_decode_body<T, OSD_BOX_CLS_CE>(pred, rois, counts, scores, boxes, logits_out, reg_out, n, max_rois, shots, pstride, wx, wy, ww,
+                                     wh, clip, img_h, img_w, score_thresh, img_hw);
+}
+
+// the one-logit modes: the score is the same sigmoid in both, so one instantiation serves them
+template <typename T>
+__global__ void box_decode_sigmoid_kernel(const T* __restrict__ pred, const float* __restrict__ rois,
+                                          const int32_t* __restrict__ counts, float* __restrict__ scores, float* __restrict__ boxes,
+                                          float* __restrict__ logits_out, float* __restrict__ reg_out, int n, int max_rois,
+                                          int shots, int pstride, float wx, float wy, float ww, float wh, float clip, float img_h,
+                                          float img_w, float score_thresh, const float* __restrict__ img_hw) {
+  box_decode_body<T, OSD_BOX_CLS_FOCAL>(pred, rois, counts, scores, boxes, logits_out, reg_out, n, max_rois, shots, pstride, wx, wy,
+                                        ww, wh, clip, img_h, img_w, score_thresh, img_hw);
 }
 
 // add_gt_proposals (modeling/rpn/fcos/inference.py:139-160): per image the kept proposals followed by the ground-truth
@@ -408,24 +449,43 @@ extern "C" int osd_groupnorm_act_rois(const void* x, const void* addend, const f
   return osd_check_launch("groupnorm_act_rois");
 }
 
-extern "C" int osd_box_decode(const void* pred, const float* rois, const int32_t* counts, float* scores, float* boxes,
-                              float* logits_out, float* reg_out, int n, int max_rois, int shots, int pred_stride,
-                              const float* reg_weights, float img_h, float img_w, const float* img_hw, float score_thresh,
-                              int dtype, void* stream) {
-  if (!pred || !rois || !scores || !boxes || !reg_weights || shots < 1 || pred_stride < 10)
+extern "C" int osd_box_decode_opt(const void* pred, const float* rois, const int32_t* counts, float* scores, float* boxes,
+                                  float* logits_out, float* reg_out, int n, int max_rois, int shots, int pred_stride,
+                                  const float* reg_weights, float img_h, float img_w, const float* img_hw, float score_thresh,
+                                  int dtype, int cls_loss, void* stream) {
+  if (cls_loss != OSD_BOX_CLS_CE && cls_loss != OSD_BOX_CLS_FOCAL && cls_loss != OSD_BOX_CLS_MSE)
+    return osd_fail(OSD_ERR_INVALID_ARG, "box_decode: cls_loss %d (OSD_BOX_CLS_CE / _FOCAL / _MSE)", cls_loss);
+  const bool ce = cls_loss == OSD_BOX_CLS_CE;
+  if (!pred || !rois || !scores || !boxes || !reg_weights || shots < 1 || pred_stride < (ce ? 10 : 9))
     return osd_fail(OSD_ERR_INVALID_ARG, "box_decode: bad args");
   if (n * max_rois == 0) return OSD_OK;
   const float clip = 4.135166556742356f;   // log(1000/16), box_coder.py:19
   const int g = grid_for((long long)n * max_rois, 256);
-  if (dtype == OSD_F32)
+  if (dtype == OSD_F32 && ce)
     hipLaunchKernelGGL(box_decode_kernel<float>, dim3(g), dim3(256), 0, OSD_STREAM(stream), (const float*)pred, rois, counts,
                        scores, boxes, logits_out, reg_out, n, max_rois, shots, pred_stride, reg_weights[0], reg_weights[1],
                        reg_weights[2], reg_weights[3], clip, img_h, img_w, score_thresh, img_hw);
-  else if (dtype == OSD_BF16)
+  else if (dtype == OSD_BF16 && ce)
     hipLaunchKernelGGL(box_decode_kernel<__bf16>, dim3(g), dim3(256), 0, OSD_STREAM(stream), (const __bf16*)pred, rois, counts,
                        scores, boxes, logits_out, reg_out, n, max_rois, shots, pred_stride, reg_weights[0], reg_weights[1],
+                       reg_weights[2], reg_weights[3], clip, img_h, img_w, score_thresh, img_hw);
+  else if (dtype == OSD_F32)
+    hipLaunchKernelGGL(box_decode_sigmoid_kernel<float>, dim3(g), dim3(256), 0, OSD_STREAM(stream), (const float*)pred, rois, counts,
+                       scores, boxes, logits_out, reg_out, n, max_rois, shots, pred_stride, reg_weights[0], reg_weights[1],
+                       reg_weights[2], reg_weights[3], clip, img_h, img_w, score_thresh, img_hw);
+  else if (dtype == OSD_BF16)
+    hipLaunchKernelGGL(box_decode_sigmoid_kernel<__bf16>, dim3(g), dim3(256), 0, OSD_STREAM(stream), (const __bf16*)pred, rois,
+                       counts, scores, boxes, logits_out, reg_out, n, max_rois, shots, pred_stride, reg_weights[0], reg_weights[1],
                        reg_weights[2], reg_weights[3], clip, img_h, img_w, score_thresh, img_hw);
   else
     return osd_fail(OSD_ERR_INVALID_ARG, "bad dtype %d", dtype);
   return osd_check_launch("box_decode");
+}
+
+extern "C" int osd_box_decode(const void* pred, const float* rois, const int32_t* counts, float* scores, float* boxes,
+                              float* logits_out, float* reg_out, int n, int max_rois, int shots, int pred_stride,
+                              const float* reg_weights, float img_h, float img_w, const float* img_hw, float score_thresh,
+                              int dtype, void* stream) {
+  return osd_box_decode_opt(pred, rois, counts, scores, boxes, logits_out, reg_out, n, max_rois, shots, pred_stride, reg_weights,
+                            img_h, img_w, img_hw, score_thresh, dtype, OSD_BOX_CLS_CE, stream);
 }

@@ -9,6 +9,7 @@
 //       (modeling/poolers.py:93-124, csrc/cuda/ROIAlign_cuda.cu:178-254)
 // The convolutions / fully connected layers run forward, data gradient and weight gradient on the implicit-GEMM kernels.
 #include "osd_common.h"
+#include "../../include/oneshotdet_hip_box_modes.h"
 
 namespace {
 
@@ -219,25 +220,66 @@ __global__ void __launch_bounds__(1024) box_match_sample_kernel(
   if (t == 0) s_count[img] = kept;
 }
 
-// Loss of the sampled ROIs (loss.py:306-381 with gt_label == -1, 'ce_loss', class-specific regression; weights of
-// box_head.py:193-194 folded in) and its gradient w.r.t. the predictor's output.  One workgroup; fixed summation order.
-template <typename T>
-__global__ void __launch_bounds__(1024) box_loss_kernel(const T* __restrict__ pred, const int32_t* __restrict__ labels,
-                                                        const float* __restrict__ targets, const int32_t* __restrict__ s_count,
-                                                        int n_img, int S, int pstride, float w_cls, float w_box,
-                                                        float* __restrict__ losses, T* __restrict__ d_pred, int gstride) {
+// Sigmoid focal loss of one logit and its derivative in the reference's CUDA form (csrc/cuda/SigmoidFocalLoss_cuda.cu:21-101, one
+// class: label 1 is the positive term, label 0 the negative one), as loss.hip computes it for the first stage: stable log-sigmoid.
+__device__ __forceinline__ float box_focal_value(float x, int label, float gamma, float alpha) {
+  const float p = 1.f / (1.f + expf(-x));
+  if (label == 1) return -alpha * powf(1.f - p, gamma) * logf(fmaxf(p, 1.17549435e-38f));
+  const float ge = x >= 0.f ? 1.f : 0.f;
+  return -(1.f - alpha) * powf(p, gamma) * (-1.f * x * ge - logf(1.f + expf(x - 2.f * x * ge)));
+}
+
+__device__ __forceinline__ float box_focal_grad(float x, int label, float gamma, float alpha) {
+  const float p = 1.f / (1.f + expf(-x));
+  if (label == 1) return -alpha * powf(1.f - p, gamma) * (1.f - p - (p * gamma * logf(fmaxf(p, 1.17549435e-38f))));
+  const float ge = x >= 0.f ? 1.f : 0.f;
+  return -(1.f - alpha) * powf(p, gamma) * ((-1.f * x * ge - logf(1.f + expf(x - 2.f * x * ge))) * (1.f - p) * gamma - p);
+}
+
+// Loss of the sampled ROIs (loss.py:306-393 with gt_label == -1, class-specific regression; weights of box_head.py:193-194
+// folded in) and its gradient w.r.t. the predictor's output.  One workgroup; fixed summation order.
+// MODE = FEW_SHOT.SECOND_STAGE_CLS_LOSS (include/oneshotdet_hip_box_modes.h): a row is L logits + 2 x 4 deltas,
+//   OSD_BOX_CLS_CE     L = 2, softmax cross-entropy, mean over the valid rows (loss.py:359): the config of record
+//   OSD_BOX_CLS_FOCAL  L = 1, sigmoid focal loss, summed / max(n_pos, 1) (loss.py:343-347)
+//   OSD_BOX_CLS_MSE    L = 1, loss.py:362-363: sigmoid(logits) [M,1] - labels.float() [M] broadcasts to [M,M], so the reference's
+//                      mean runs over M x M pairs: mean_ij (s_i - l_j)^2 = mean_i (s_i - ml)^2 + ml (1 - ml), ml = n_pos / M
+//                      (labels 0 / 1).  Summed in that form: every term is non-negative, nothing cancels.
+// The smooth-L1 term, the reduction, the NaN poisoning of labels > 1 and the zeroing of invalid rows are one chain for all modes.
+template <typename T, int MODE>
+__device__ __forceinline__ void box_loss_body(const T* __restrict__ pred, const int32_t* __restrict__ labels,
+                                              const float* __restrict__ targets, const int32_t* __restrict__ s_count,
+                                              int n_img, int S, int pstride, float w_cls, float w_box, float gamma, float alpha,
+                                              float* __restrict__ losses, T* __restrict__ d_pred, int gstride) {
+  constexpr int L = MODE == OSD_BOX_CLS_CE ? 2 : 1;
   __shared__ float red[2][1024];
-  __shared__ int nval, bad_label;
+  __shared__ int nval, bad_label, npos_all;
   const int t = threadIdx.x;
   if (t == 0) {
     int n = 0;
     for (int i = 0; i < n_img; ++i) n += min(s_count[i], S);
     nval = n;
     bad_label = 0;
+    npos_all = 0;
   }
   __syncthreads();
   const int M = n_img * S;
   const float inv_n = nval > 0 ? 1.f / (float)nval : 0.f;
+  float inv_pos = 0.f, ml = 0.f;          // 1 / max(n_pos, 1) (focal); mean label n_pos / valid rows (mse)
+  if constexpr (MODE != OSD_BOX_CLS_CE) {
+    // both normalisers need n_pos before the first gradient is written: count the valid positives first (integers: any order)
+    int c = 0;
+    for (int r = t; r < M; r += 1024) {
+      const int img = r / S, ri = r - img * S;
+      c += (ri < min(s_count[img], S) && labels[r] > 0) ? 1 : 0;
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d, 64);
+    if ((t & 63) == 0 && c) atomicAdd(&npos_all, c);
+    __syncthreads();
+    const int n_pos = npos_all;
+    inv_pos = 1.f / (float)max(n_pos, 1);
+    ml = (float)n_pos * inv_n;
+  }
   float lc = 0.f, lb = 0.f;
   for (int r = t; r < M; r += 1024) {
     const int img = r / S, ri = r - img * S;
@@ -247,27 +289,38 @@ __global__ void __launch_bounds__(1024) box_loss_kernel(const T* __restrict__ pr
     if (!valid) continue;
     const T* p = pred + (size_t)r * pstride;
     // two classes (background / the queried object: ROI_BOX_HEAD.NUM_CLASSES = 2 in the config of record); a row is
-    // 2 logits + 2 x 4 deltas.  A label > 1 has no columns in the row: nothing is read or written for it and the
+    // L logits + 2 x 4 deltas.  A label > 1 has no columns in the row: nothing is read or written for it and the
     // losses come back NaN (no host synchronisation to report it any other way)
     if (labels[r] > 1) { bad_label = 1; continue; }
     const int l = labels[r] > 0 ? labels[r] : 0;
-    const float x0 = to_f32(p[0]), x1 = to_f32(p[1]);
-    const float m = fmaxf(x0, x1);
-    const float e0 = expf(x0 - m), e1 = expf(x1 - m);
-    const float lse = m + logf(e0 + e1);
-    lc += lse - (l == 1 ? x1 : x0);
-    if (g) {
-      const float s0 = e0 / (e0 + e1), s1 = e1 / (e0 + e1);
-      g[0] = from_f32<T>(w_cls * inv_n * (s0 - (l == 0 ? 1.f : 0.f)));
-      g[1] = from_f32<T>(w_cls * inv_n * (s1 - (l == 1 ? 1.f : 0.f)));
+    if constexpr (MODE == OSD_BOX_CLS_CE) {
+      const float x0 = to_f32(p[0]), x1 = to_f32(p[1]);
+      const float m = fmaxf(x0, x1);
+      const float e0 = expf(x0 - m), e1 = expf(x1 - m);
+      const float lse = m + logf(e0 + e1);
+      lc += lse - (l == 1 ? x1 : x0);
+      if (g) {
+        const float s0 = e0 / (e0 + e1), s1 = e1 / (e0 + e1);
+        g[0] = from_f32<T>(w_cls * inv_n * (s0 - (l == 0 ? 1.f : 0.f)));
+        g[1] = from_f32<T>(w_cls * inv_n * (s1 - (l == 1 ? 1.f : 0.f)));
+      }
+    } else if constexpr (MODE == OSD_BOX_CLS_FOCAL) {
+      const float x = to_f32(p[0]);
+      lc += box_focal_value(x, l, gamma, alpha);
+      if (g) g[0] = from_f32<T>(w_cls * inv_pos * box_focal_grad(x, l, gamma, alpha));
+    } else {
+      const float s = 1.f / (1.f + expf(-to_f32(p[0])));
+      const float d = s - ml;
+      lc += d * d;
+      if (g) g[0] = from_f32<T>(w_cls * 2.f * inv_n * d * s * (1.f - s));
     }
     if (l >= 1) {
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
-        const float d = to_f32(p[2 + 4 * l + k]) - targets[(size_t)r * 4 + k];
+        const float d = to_f32(p[L + 4 * l + k]) - targets[(size_t)r * 4 + k];
         const float n = fabsf(d);
         lb += n < 1.f ? 0.5f * n * n : n - 0.5f;                       // smooth_l1_loss(beta = 1), summed
-        if (g) g[2 + 4 * l + k] = from_f32<T>(w_box * inv_n * (n < 1.f ? d : (d > 0.f ? 1.f : -1.f)));
+        if (g) g[L + 4 * l + k] = from_f32<T>(w_box * inv_n * (n < 1.f ? d : (d > 0.f ? 1.f : -1.f)));
       }
     }
   }
@@ -280,10 +333,34 @@ __global__ void __launch_bounds__(1024) box_loss_kernel(const T* __restrict__ pr
   }
   if (t == 0) {
     const float poison = bad_label ? __builtin_nanf("") : 0.f;
-    losses[0] = w_cls * red[0][0] * inv_n + poison;     // 5 * F.cross_entropy(class_logits, labels)
+    if constexpr (MODE == OSD_BOX_CLS_CE)
+      losses[0] = w_cls * red[0][0] * inv_n + poison;     // 5 * F.cross_entropy(class_logits, labels)
+    else if constexpr (MODE == OSD_BOX_CLS_FOCAL)
+      losses[0] = w_cls * red[0][0] * inv_pos + poison;   // 5 * SigmoidFocalLoss(...).sum() / max(n_pos, 1)
+    else
+      losses[0] = w_cls * (red[0][0] * inv_n + ml * (1.f - ml)) + poison;   // 5 * mean over [M,M] of (sigmoid - labels)^2
     losses[1] = w_box * red[1][0] * inv_n + poison;     // 2.5 * smooth_l1(sum) / labels.numel()
     losses[2] = (float)nval;
   }
+}
+
+// 'ce_loss', the config of record: the launch osd_box_loss has always made
+template <typename T>
+__global__ void __launch_bounds__(1024) box_loss_kernel(const T* __restrict__ pred, const int32_t* __restrict__ labels,
+                                                        const float* __restrict__ targets, const int32_t* __restrict__ s_count,
+                                                        int n_img, int S, int pstride, float w_cls, float w_box,
+                                                        float* __restrict__ losses, T* __restrict__ d_pred, int gstride) {
+  box_loss_body<T, OSD_BOX_CLS_CE>(pred, labels, targets, s_count, n_img, S, pstride, w_cls, w_box, 0.f, 0.f, losses, d_pred, gstride);
+}
+
+// the one-logit modes
+template <typename T, int MODE>
+__global__ void __launch_bounds__(1024) box_loss_mode_kernel(const T* __restrict__ pred, const int32_t* __restrict__ labels,
+                                                             const float* __restrict__ targets, const int32_t* __restrict__ s_count,
+                                                             int n_img, int S, int pstride, float w_cls, float w_box, float gamma,
+                                                             float alpha, float* __restrict__ losses, T* __restrict__ d_pred,
+                                                             int gstride) {
+  box_loss_body<T, MODE>(pred, labels, targets, s_count, n_img, S, pstride, w_cls, w_box, gamma, alpha, losses, d_pred, gstride);
 }
 
 __device__ __forceinline__ void ld2(const float* p, float& a, float& b) {
@@ -546,20 +623,48 @@ extern "C" int osd_box_match_sample(const float* boxes, const int32_t* counts, c
   return osd_check_launch("box_match_sample");
 }
 
-extern "C" int osd_box_loss(const void* pred, const int32_t* labels, const float* targets, const int32_t* s_count, int n,
-                            int rois_per_image, int pred_stride, float w_cls, float w_box, float* losses, void* d_pred,
-                            int grad_stride, int dtype, void* stream) {
+template <typename T>
+static void launch_box_loss(const void* pred, const int32_t* labels, const float* targets, const int32_t* s_count, int n, int S,
+                            int pstride, float w_cls, float w_box, float* losses, void* d_pred, int gstride, int cls_loss,
+                            float gamma, float alpha, hipStream_t st) {
+  const T* p = (const T*)pred;
+  T* d = (T*)d_pred;
+  if (cls_loss == OSD_BOX_CLS_CE)
+    hipLaunchKernelGGL(box_loss_kernel<T>, dim3(1), dim3(1024), 0, st, p, labels, targets, s_count, n, S, pstride, w_cls, w_box,
+                       losses, d, gstride);
+  else if (cls_loss == OSD_BOX_CLS_FOCAL)
+    hipLaunchKernelGGL((box_loss_mode_kernel<T, OSD_BOX_CLS_FOCAL>), dim3(1), dim3(1024), 0, st, p, labels, targets, s_count, n, S,
+                       pstride, w_cls, w_box, gamma, alpha, losses, d, gstride);
+  else
+    hipLaunchKernelGGL((box_loss_mode_kernel<T, OSD_BOX_CLS_MSE>), dim3(1), dim3(1024), 0, st, p, labels, targets, s_count, n, S,
+                       pstride, w_cls, w_box, gamma, alpha, losses, d, gstride);
+}
+
+extern "C" int osd_box_loss_opt(const void* pred, const int32_t* labels, const float* targets, const int32_t* s_count, int n,
+                                int rois_per_image, int pred_stride, float w_cls, float w_box, float* losses, void* d_pred,
+                                int grad_stride, int dtype, int cls_loss, float gamma, float alpha, void* stream) {
   if (!pred || !labels || !targets || !s_count || !losses) return osd_fail(OSD_ERR_INVALID_ARG, "box_loss: null argument");
-  if (pred_stride < 10 || (d_pred && grad_stride < 10)) return osd_fail(OSD_ERR_INVALID_ARG, "box_loss: 2 logits + 8 deltas per row");
+  if (cls_loss != OSD_BOX_CLS_CE && cls_loss != OSD_BOX_CLS_FOCAL && cls_loss != OSD_BOX_CLS_MSE)
+    return osd_fail(OSD_ERR_INVALID_ARG, "box_loss: cls_loss %d (OSD_BOX_CLS_CE / _FOCAL / _MSE)", cls_loss);
+  const int width = (cls_loss == OSD_BOX_CLS_CE ? 2 : 1) + 8;
+  if (pred_stride < width || (d_pred && grad_stride < width))
+    return osd_fail(OSD_ERR_INVALID_ARG, "box_loss: %d logits + 8 deltas per row", width - 8);
   if (dtype == OSD_F32)
-    hipLaunchKernelGGL(box_loss_kernel<float>, dim3(1), dim3(1024), 0, OSD_STREAM(stream), (const float*)pred, labels, targets,
-                       s_count, n, rois_per_image, pred_stride, w_cls, w_box, losses, (float*)d_pred, grad_stride);
+    launch_box_loss<float>(pred, labels, targets, s_count, n, rois_per_image, pred_stride, w_cls, w_box, losses, d_pred, grad_stride,
+                           cls_loss, gamma, alpha, OSD_STREAM(stream));
   else if (dtype == OSD_BF16)
-    hipLaunchKernelGGL(box_loss_kernel<__bf16>, dim3(1), dim3(1024), 0, OSD_STREAM(stream), (const __bf16*)pred, labels, targets,
-                       s_count, n, rois_per_image, pred_stride, w_cls, w_box, losses, (__bf16*)d_pred, grad_stride);
+    launch_box_loss<__bf16>(pred, labels, targets, s_count, n, rois_per_image, pred_stride, w_cls, w_box, losses, d_pred, grad_stride,
+                            cls_loss, gamma, alpha, OSD_STREAM(stream));
   else
     return osd_fail(OSD_ERR_INVALID_ARG, "box_loss: bad dtype");
   return osd_check_launch("box_loss");
+}
+
+extern "C" int osd_box_loss(const void* pred, const int32_t* labels, const float* targets, const int32_t* s_count, int n,
+                            int rois_per_image, int pred_stride, float w_cls, float w_box, float* losses, void* d_pred,
+                            int grad_stride, int dtype, void* stream) {
+  return osd_box_loss_opt(pred, labels, targets, s_count, n, rois_per_image, pred_stride, w_cls, w_box, losses, d_pred, grad_stride,
+                          dtype, OSD_BOX_CLS_CE, 0.f, 0.f, stream);
 }
 
 extern "C" int osd_groupnorm_act_rois_bwd(const void* x, const void* addend, const float* gamma, const float* beta,

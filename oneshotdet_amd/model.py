@@ -366,9 +366,14 @@ class HotPathEngine(object):
     the query goes through the target's backbone (generalized_rcnn.py:274-275): ONE packed BackboneWeights serves both
     branches (`supp_backbone` is the same object), and `supp_backbone.*` entries of the state_dict are dropped.
     supp_roialign (FEW_SHOT.SUPP_ROIALIGN): True = the query pyramid is pooled by a 1 x 1 ROIAlign of each query's box; False =
-    by its global average (run_query_pool).  The pooling has no weights: a state_dict does not tell the two apart."""
+    by its global average (run_query_pool).  The pooling has no weights: a state_dict does not tell the two apart.
+    box_cls_loss (FEW_SHOT.SECOND_STAGE_CLS_LOSS): "ce_loss" = two class logits and a softmax score; "focal_loss" / "mse_loss" = ONE
+    logit and a sigmoid score (roi_box_predictors.py:47-50, inference.py:61-69).  A state_dict whose cls_score has the other mode's
+    row count is refused (ValueError naming the option)."""
 
-    def __init__(self, state_dict, dtype=torch.float32, device="cuda", siamese_backbone=True, supp_roialign=True):
+    def __init__(self, state_dict, dtype=torch.float32, device="cuda", siamese_backbone=True, supp_roialign=True,
+                 box_cls_loss="ce_loss"):
+        self.box_cls_loss = spec.box_cls_loss_mode(box_cls_loss)              # ValueError before anything is built
         if not torch.cuda.is_available():
             raise ops._lib.OsdError("HotPathEngine needs an MI355X: no GPU visible and there is no CPU fallback")
         ops._lib.load()
@@ -392,7 +397,7 @@ class HotPathEngine(object):
         self.box_head = None
         if all(k in self.sd for k in spec.box_head_shapes()):
             from .box_head import BoxHeadWeights
-            self.box_head = BoxHeadWeights(self.sd, self.dtype)
+            self.box_head = BoxHeadWeights(self.sd, self.dtype, box_cls_loss=self.box_cls_loss)
 
     def tune(self, images, queries, second_stage=False):
         """Pick, by measurement on this device, the conv algorithm (kernel generation, ring depth, tile) for every
@@ -450,6 +455,9 @@ class HotPathEngine(object):
             query_sizes = queries.image_sizes
         if isinstance(queries, ImageList):
             queries, query_sizes = queries.tensors, queries.image_sizes
+        if second_stage:                        # refused before anything is launched
+            from .box_head import check_shots
+            check_shots(self.box_cls_loss, queries.shape[0] // images.shape[0])
         out = self.forward(images, queries, concurrent, query_sizes)
         h, w = images.shape[-2:]
         pre = spec.PRE_NMS_TOP_N_TRAIN if training else spec.PRE_NMS_TOP_N_TEST

@@ -1302,9 +1302,11 @@ def groupnorm_act_rois(x, gamma, beta, groups=32, eps=1e-5, slope=0.2, addend=No
     return out
 
 
-def box_decode(pred, rois, counts, reg_weights, img_h, img_w, score_thresh, want_raw=False, img_hw=None):
-    """pred [S, N*R, P] (cols 0..1 logits, 2..9 deltas), rois [N,R,4] -> scores [N,R] (-1 = dropped), boxes [N,R,4]
-    (+ the selected logits [N*R,2] and deltas [N*R,8] in fp32 when want_raw)."""
+def box_decode(pred, rois, counts, reg_weights, img_h, img_w, score_thresh, want_raw=False, img_hw=None, cls_loss="ce_loss"):
+    """pred [S, N*R, P] (L logits, then 8 deltas; L = 2 for cls_loss 'ce_loss', 1 for 'focal_loss' / 'mse_loss' whose score is
+    sigmoid(logit)), rois [N,R,4] -> scores [N,R] (-1 = dropped), boxes [N,R,4] (+ the selected logits [N*R,L] and deltas [N*R,8]
+    in fp32 when want_raw)."""
+    mode = spec.BOX_CLS_LOSSES.index(spec.box_cls_loss_mode(cls_loss))
     _chk_dev(pred, rois, counts)
     s, m, p = pred.shape
     n, r, _ = rois.shape
@@ -1312,11 +1314,15 @@ def box_decode(pred, rois, counts, reg_weights, img_h, img_w, score_thresh, want
     dev = pred.device
     scores = torch.empty((n, r), device=dev, dtype=torch.float32)
     boxes = torch.empty((n, r, 4), device=dev, dtype=torch.float32)
-    lo = torch.empty((m, 2), device=dev, dtype=torch.float32) if want_raw else None
+    lo = torch.empty((m, spec.box_cls_logits(cls_loss)), device=dev, dtype=torch.float32) if want_raw else None
     ro = torch.empty((m, 8), device=dev, dtype=torch.float32) if want_raw else None
     rw = (C.c_float * 4)(*[float(v) for v in reg_weights])
-    _lib.call("osd_box_decode", _p(pred), _ptr(rois.contiguous()), _p(counts), _p(scores), _p(boxes), _p(lo),
-              _p(ro), n, r, s, p, rw, float(img_h), float(img_w), _p(img_hw), float(score_thresh), _dt(pred), _stream())
+    if mode == 0:
+        _lib.call("osd_box_decode", _p(pred), _ptr(rois.contiguous()), _p(counts), _p(scores), _p(boxes), _p(lo),
+                  _p(ro), n, r, s, p, rw, float(img_h), float(img_w), _p(img_hw), float(score_thresh), _dt(pred), _stream())
+    else:
+        _lib.call("osd_box_decode_opt", _p(pred), _ptr(rois.contiguous()), _p(counts), _p(scores), _p(boxes), _p(lo),
+                  _p(ro), n, r, s, p, rw, float(img_h), float(img_w), _p(img_hw), float(score_thresh), _dt(pred), mode, _stream())
     return (scores, boxes, lo, ro) if want_raw else (scores, boxes)
 
 
@@ -1344,15 +1350,25 @@ def box_match_sample(boxes, counts, gt_boxes, gt_count, keys, batch_per_image, p
     return (sb, sl, st, si, sc, al, am) if want_all else (sb, sl, st, si, sc)
 
 
-def box_loss(pred, labels, targets, s_count, n, rois_per_image, w_cls, w_box, grad_stride=0):
-    """loss.py:306-381 ('ce_loss') x the weights of box_head.py:193-194.  pred [M, stride] (cols 0..1 logits, 2..9 deltas)
+def box_loss(pred, labels, targets, s_count, n, rois_per_image, w_cls, w_box, grad_stride=0, cls_loss="ce_loss", gamma=None,
+             alpha=None):
+    """loss.py:306-393 x the weights of box_head.py:193-194.  pred [M, stride] (L logits, then 8 deltas; cls_loss 'ce_loss':
+    L = 2, cross-entropy; 'focal_loss': L = 1, sigmoid focal loss (gamma, alpha: spec.LOSS_GAMMA, spec.BOX_LOSS_ALPHA) summed /
+    max(positives, 1); 'mse_loss': L = 1, the reference's [M, M]-broadcast mean of (sigmoid - label)^2)
     -> losses [3] = (classification, box regression, valid rows) and, with grad_stride, d_pred [M, grad_stride]."""
+    mode = spec.BOX_CLS_LOSSES.index(spec.box_cls_loss_mode(cls_loss))
     m = n * rois_per_image
     pred2 = pred.reshape(m, -1)
     losses = torch.empty((3,), device=pred.device, dtype=torch.float32)
     d = torch.empty((m, grad_stride), device=pred.device, dtype=pred.dtype) if grad_stride else None
-    _lib.call("osd_box_loss", _p(pred2), _p(labels), _p(targets), _p(s_count), n, rois_per_image, pred2.shape[1],
-              float(w_cls), float(w_box), _p(losses), _p(d), int(grad_stride), _dt(pred), _stream())
+    if mode == 0:
+        _lib.call("osd_box_loss", _p(pred2), _p(labels), _p(targets), _p(s_count), n, rois_per_image, pred2.shape[1],
+                  float(w_cls), float(w_box), _p(losses), _p(d), int(grad_stride), _dt(pred), _stream())
+    else:
+        _lib.call("osd_box_loss_opt", _p(pred2), _p(labels), _p(targets), _p(s_count), n, rois_per_image, pred2.shape[1],
+                  float(w_cls), float(w_box), _p(losses), _p(d), int(grad_stride), _dt(pred), mode,
+                  float(spec.LOSS_GAMMA if gamma is None else gamma), float(spec.BOX_LOSS_ALPHA if alpha is None else alpha),
+                  _stream())
     return losses, d
 
 

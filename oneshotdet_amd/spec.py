@@ -48,6 +48,9 @@ BOX_FG_IOU_THRESH = 0.5               # ROI_HEADS.FG_IOU_THRESHOLD == BG_IOU_THR
 BOX_BATCH_PER_IMAGE = 128             # ROI_HEADS.BATCH_SIZE_PER_IMAGE
 BOX_POSITIVE_FRACTION = 0.25          # ROI_HEADS.POSITIVE_FRACTION
 BOX_LOSS_WEIGHTS = (5.0, 2.5)         # loss_classifier *= 5; loss_box_reg *= 2.5
+BOX_CLS_LOSS = "ce_loss"               # yaml / defaults.py:511 FEW_SHOT.SECOND_STAGE_CLS_LOSS
+BOX_CLS_LOSSES = ("ce_loss", "focal_loss", "mse_loss")      # index = OSD_BOX_CLS_* of include/oneshotdet_hip_box_modes.h
+BOX_LOSS_ALPHA = 0.25                 # FEW_SHOT.SECOND_STAGE_LOSS_ALPHA (defaults.py:512); gamma is FCOS.LOSS_GAMMA (box_head/loss.py:40-44)
 LEVEL_MAP_SCALE = 224                 # poolers.py:16 LevelMapper canonical_scale / canonical_level / eps
 LEVEL_MAP_LEVEL = 4
 LEVEL_MAP_EPS = 1e-6
@@ -58,6 +61,52 @@ def loss_mode(center_sample, loc_loss_type):
     if loc_loss_type not in LOC_LOSS_TYPES:
         raise ValueError("loc_loss_type must be one of %s (FCOS.LOC_LOSS_TYPE), not %r" % (", ".join(LOC_LOSS_TYPES), loc_loss_type))
     return bool(center_sample), str(loc_loss_type)
+
+
+_BOX_CLS_REFUSED = {
+    "l1_loss": "it needs FEW_SHOT.SOFT_LABELING (IoU soft labels carried through the sampler, box_head/loss.py:52-64,364-365)",
+    "cxe_loss": "it needs FEW_SHOT.SOFT_LABELING (IoU soft labels carried through the sampler, box_head/loss.py:52-64,366-367)",
+}
+
+
+def box_cls_loss_mode(box_cls_loss, loss_weighted=False, neg_support=False, method="concat"):
+    """-> the validated FEW_SHOT.SECOND_STAGE_CLS_LOSS name; ValueError for a loss box_head/loss.py:343-369 does not have and, by
+    name, for what it has that this build does not support: 'l1_loss' / 'cxe_loss', FEW_SHOT.LOSS_WEIGHTED (its reference path
+    calls .cuda() unconditionally, loss.py:349-357: nothing to record it against), negative support and SECOND_STAGE_METHOD 'rn'."""
+    if loss_weighted:
+        raise ValueError("FEW_SHOT.LOSS_WEIGHTED is not supported (box_head/loss.py:349-357)")
+    if neg_support:
+        raise ValueError("FEW_SHOT.NEG_SUPPORT is not supported: the second stage runs without negative support")
+    if method != "concat":
+        raise ValueError("FEW_SHOT.SECOND_STAGE_METHOD %r is not supported: only 'concat' (not 'rn' or 'matching')" % (method,))
+    if box_cls_loss in _BOX_CLS_REFUSED:
+        raise ValueError("box_cls_loss %r is not supported: %s" % (box_cls_loss, _BOX_CLS_REFUSED[box_cls_loss]))
+    if box_cls_loss not in BOX_CLS_LOSSES:
+        raise ValueError("box_cls_loss must be one of %s (FEW_SHOT.SECOND_STAGE_CLS_LOSS), not %r"
+                         % (", ".join(BOX_CLS_LOSSES), box_cls_loss))
+    return str(box_cls_loss)
+
+
+def box_cls_logits(box_cls_loss="ce_loss"):
+    """Outputs of predictor.cls_score = logits at the head of a predictor row (roi_box_predictors.py:47-50,66-68,76-77): 2 for
+    'ce_loss', 1 for the sigmoid losses."""
+    return BOX_NUM_CLASSES if box_cls_loss_mode(box_cls_loss) == "ce_loss" else 1
+
+
+def check_box_cls_score(sd, box_cls_loss, prefix="roi_heads.box.", who="the engine"):
+    """The state_dict's cls_score must have the mode's row count: a 1-row cls_score read as 2 logits (or the reverse) shifts
+    every box delta by a column and detects garbage without an error."""
+    want = box_cls_logits(box_cls_loss)
+    for leaf in ("weight", "bias"):
+        rows = int(sd[prefix + "predictor.cls_score." + leaf].shape[0])
+        if rows != want:
+            other = [m for m in BOX_CLS_LOSSES if box_cls_logits(m) == rows]
+            raise ValueError("%spredictor.cls_score.%s has %d row(s) but box_cls_loss=%r has %d logit(s) per ROI%s"
+                             % (prefix, leaf, rows, box_cls_loss, want,
+                                ": build %s with box_cls_loss=%s" % (who, " or ".join(repr(m) for m in other)) if other else ""))
+    rows = int(sd[prefix + "predictor.bbox_pred.weight"].shape[0])
+    if rows != 4 * BOX_NUM_CLASSES:
+        raise ValueError("%spredictor.bbox_pred.weight has %d rows, expected %d" % (prefix, rows, 4 * BOX_NUM_CLASSES))
 
 
 def _bn(prefix, n, out):
@@ -126,11 +175,14 @@ def fcos_head_shapes(prefix="rpn.head."):
     return out
 
 
-def box_head_shapes(prefix="roi_heads.box."):
+def box_head_shapes(prefix="roi_heads.box.", box_cls_loss="ce_loss"):
     """Second-stage few-shot ROI box head keys (modeling/roi_heads/box_head/box_head.py:40-78: compress_dim_conv =
     Sequential(conv1x1, GN, LeakyReLU, conv1x1, GN, LeakyReLU) -> indices 0,1,3,4; feature_aggreg = Sequential(conv3x3,
-    GN, LeakyReLU); fc6/fc7 make_fc; roi_box_predictors.py:37-99 FPNPredictor with 2 classes and 2x4 box deltas)."""
+    GN, LeakyReLU); fc6/fc7 make_fc; roi_box_predictors.py:37-99 FPNPredictor with 2 classes and 2x4 box deltas).
+    box_cls_loss (FEW_SHOT.SECOND_STAGE_CLS_LOSS): cls_score has 2 outputs for 'ce_loss' and ONE for 'focal_loss' / 'mse_loss'
+    (roi_box_predictors.py:47-50,66-68,76-77); bbox_pred keeps its 8."""
     out = OrderedDict()
+    n_logits = box_cls_logits(box_cls_loss)
     c2 = 2 * FPN_OUT
     out[prefix + "compress_dim_conv.0.weight"] = (c2, c2, 1, 1)
     out[prefix + "compress_dim_conv.0.bias"] = (c2,)
@@ -148,8 +200,8 @@ def box_head_shapes(prefix="roi_heads.box."):
     out[prefix + "fc6.bias"] = (BOX_MLP_DIM,)
     out[prefix + "fc7.weight"] = (BOX_MLP_DIM, BOX_MLP_DIM)
     out[prefix + "fc7.bias"] = (BOX_MLP_DIM,)
-    out[prefix + "predictor.cls_score.weight"] = (BOX_NUM_CLASSES, BOX_MLP_DIM)
-    out[prefix + "predictor.cls_score.bias"] = (BOX_NUM_CLASSES,)
+    out[prefix + "predictor.cls_score.weight"] = (n_logits, BOX_MLP_DIM)
+    out[prefix + "predictor.cls_score.bias"] = (n_logits,)
     out[prefix + "predictor.bbox_pred.weight"] = (BOX_NUM_CLASSES * 4, BOX_MLP_DIM)
     out[prefix + "predictor.bbox_pred.bias"] = (BOX_NUM_CLASSES * 4,)
     return out
@@ -166,11 +218,11 @@ def hot_path_shapes(siamese_backbone=True):
     return out
 
 
-def full_model_shapes(siamese_backbone=True):
+def full_model_shapes(siamese_backbone=True, box_cls_loss="ce_loss"):
     """Hot path + second-stage box head = every state_dict entry of the reference model under the config of record
-    (siamese_backbone: see hot_path_shapes)."""
+    (siamese_backbone: see hot_path_shapes; box_cls_loss: see box_head_shapes)."""
     out = hot_path_shapes(siamese_backbone)
-    out.update(box_head_shapes())
+    out.update(box_head_shapes(box_cls_loss=box_cls_loss))
     return out
 
 

@@ -24,6 +24,10 @@ center_sample / loc_loss_type (FCOS.CENTER_SAMPLE / FCOS.LOC_LOSS_TYPE, fcos/los
 locations are positive (True: inside a box's sampling region; False: inside the whole box) and the regression loss ("giou", "iou" =
 -log(iou), "linear_iou" = 1 - iou).  The defaults (True, "giou") are the config of record; the reference's own defaults are
 (False, "iou").  Only the loss kernels' instantiation changes: the step has the same launches in every mode.
+
+box_cls_loss (FEW_SHOT.SECOND_STAGE_CLS_LOSS, box_head/loss.py:343-363; second_stage=True only): "ce_loss" (the config of record),
+"focal_loss" or "mse_loss".  The two sigmoid losses have ONE class logit (roi_box_predictors.py:47-50): the predictor conv has 9
+rows instead of 10 and the loss launch is another instantiation of the same kernel body; everything else in the step is the same.
 """
 import math
 import os
@@ -91,8 +95,9 @@ class TrainEngine(ForwardPass, BackwardPass, SecondStage, Update, State):
     def __init__(self, state_dict, dtype=torch.bfloat16, device="cuda", lr=0.0005, momentum=0.9, weight_decay=0.0001,
                  process_group=None, wgrad_side_stream=True, optimizer="fused", second_stage=False, ordered_wgrad=None,
                  exchange_single_rank=False, grad_wire_dtype=None, siamese_backbone=True, supp_roialign=True,
-                 center_sample=True, loc_loss_type="giou"):
+                 center_sample=True, loc_loss_type="giou", box_cls_loss="ce_loss"):
         self.center_sample, self.loc_loss_type = spec.loss_mode(center_sample, loc_loss_type)     # ValueError before anything is built
+        self.box_cls_loss = spec.box_cls_loss_mode(box_cls_loss)
         if not torch.cuda.is_available():
             raise ops._lib.OsdError("TrainEngine needs an MI355X: no GPU visible and there is no CPU fallback")
         ops._lib.load()
@@ -286,12 +291,14 @@ class TrainEngine(ForwardPass, BackwardPass, SecondStage, Update, State):
     def _build_box_head(self, sd):
         """roi_heads.box.* (modeling/roi_heads/box_head/box_head.py:36-79) as this build lays it out: the first 1x1 conv split
         at the concatenation into its ROI half (no bias) and its query half (+ bias), fc6 as a 1x1 conv over the (h, w, c)
-        flattening of the NHWC ROI maps, cls_score + bbox_pred as one 10-row conv.  Appended to the plan after the FCOS head:
+        flattening of the NHWC ROI maps, cls_score + bbox_pred as one conv of L + 8 rows (L = spec.box_cls_logits(self.box_cls_loss):
+        10 rows for 'ce_loss', 9 for the sigmoid losses).  Appended to the plan after the FCOS head:
         one more gradient bucket ('box_head')."""
         b = "roi_heads.box."
         missing = [k for k in spec.box_head_shapes() if k not in sd]
         if missing:
             raise KeyError("second_stage=True needs the roi_heads.box.* entries, e.g. %s" % missing[:2])
+        spec.check_box_cls_score(sd, self.box_cls_loss, b)
         c, mid, p = spec.FPN_OUT, spec.FPN_OUT // 2, spec.BOX_POOL
 
         def conv(name, cout, cin, r, s, has_bias):
@@ -310,7 +317,7 @@ class TrainEngine(ForwardPass, BackwardPass, SecondStage, Update, State):
         self._plan += [(b + "feature_aggreg.1.weight", (mid,)), (b + "feature_aggreg.1.bias", (mid,))]
         conv(b + "fc6", spec.BOX_MLP_DIM, mid * p * p, 1, 1, True)
         conv(b + "fc7", spec.BOX_MLP_DIM, spec.BOX_MLP_DIM, 1, 1, True)
-        conv(b + "pred", 5 * spec.BOX_NUM_CLASSES, spec.BOX_MLP_DIM, 1, 1, True)
+        conv(b + "pred", spec.box_cls_logits(self.box_cls_loss) + 4 * spec.BOX_NUM_CLASSES, spec.BOX_MLP_DIM, 1, 1, True)
 
     def _allocate(self, sd):
         total = sum(int(math.prod(s)) for _, s in self._plan)

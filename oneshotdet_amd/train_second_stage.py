@@ -1,5 +1,5 @@
 """The second stage inside the training step (TrainEngine mixin, second_stage=True): ROIBoxHead in training on the training
-proposals — subsample, box head forward, cross-entropy + smooth-L1, the whole backward.  Reference: box_head.py:100-203."""
+proposals — subsample, box head forward, classification loss (self.box_cls_loss) + smooth-L1, the whole backward.  Reference: box_head.py:100-203."""
 
 import torch
 
@@ -12,7 +12,8 @@ class SecondStage(object):
                                   want_debug=False):
         """ROIBoxHead in training (box_head.py:100-203) on the training proposals (ground truth appended): subsample on the
         device, box head forward on the 128 sampled ROIs per image with the FIRST query of every image (the reference returns
-        the losses from inside its loop over shots), cross-entropy + smooth-L1 with the weights 5 / 2.5, and the whole
+        the losses from inside its loop over shots), cross-entropy (or, by self.box_cls_loss, the sigmoid focal / mse loss over the one
+        logit) + smooth-L1 with the weights 5 / 2.5, and the whole
         backward on the current stream: weight / bias / GroupNorm gradients into the flat buffer, the gradient w.r.t. the
         target FPN features as fp32 level maps and w.r.t. the query features' level.
         proposals = (boxes [N,P,4], scores, counts).  keys [N,P]: uniform randoms of the sampler (default: torch.rand).
@@ -53,7 +54,7 @@ class SecondStage(object):
         f7 = ops.conv2d(f6, fc7.pc, act=ACT_RELU)
         pred = ops.conv2d(f7, cp.pc)
         losses, d_pred = ops.box_loss(pred, sl, st, sc, n, S, spec.BOX_LOSS_WEIGHTS[0], spec.BOX_LOSS_WEIGHTS[1],
-                                      grad_stride=cp.pd.cin_k)
+                                      grad_stride=cp.pd.cin_k, cls_loss=self.box_cls_loss)
         # ---- backward (inline on this stream: M = 1024 ROIs)
 
         def wg(c, xin, dy, pad=0):

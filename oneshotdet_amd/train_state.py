@@ -15,7 +15,8 @@ class State(object):
         state_dict(), named_grads() and the optimizer state alike."""
         h, b = "rpn.head.", "roi_heads.box."
         c, mid, p = spec.FPN_OUT, spec.FPN_OUT // 2, spec.BOX_POOL
-        nc = spec.BOX_NUM_CLASSES
+        nc = spec.box_cls_logits(getattr(self, "box_cls_loss", spec.BOX_CLS_LOSS))    # rows of cls_score at the head of the predictor
+        nr = 4 * spec.BOX_NUM_CLASSES                                                 # rows of bbox_pred behind them
         out = {}
         for name, shape in self._plan:
             base, leaf = name.rsplit(".", 1)
@@ -49,7 +50,7 @@ class State(object):
                 keys = [b + "predictor.cls_score." + leaf, b + "predictor.bbox_pred." + leaf]
                 if leaf == "weight":
                     out[name] = (keys, lambda ts: torch.cat(ts, 0)[:, None, None, :],
-                                 lambda v, keys=keys: {keys[0]: v[:nc].reshape(nc, -1), keys[1]: v[nc:].reshape(4 * nc, -1)})
+                                 lambda v, keys=keys: {keys[0]: v[:nc].reshape(nc, -1), keys[1]: v[nc:].reshape(nr, -1)})
                 else:
                     out[name] = (keys, lambda ts: torch.cat(ts, 0), lambda v, keys=keys: {keys[0]: v[:nc], keys[1]: v[nc:]})
             elif base in self.convs and leaf == "weight":
