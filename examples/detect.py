@@ -1,7 +1,8 @@
 """One-shot detection end to end on an MI355X with this build, the way a user of RyanXLi/OneshotDet would call it:
 
     python examples/detect.py [--checkpoint model_0040000.pth | --c2 R-50.pkl] [--dtype bf16|f32] [--second-stage]
-                              [--shared-backbone] [--no-supp-roialign] [--box-cls-loss ce_loss|focal_loss|mse_loss]
+                              [--shared-backbone] [--no-supp-roialign] [--box-cls-loss ce_loss|focal_loss|mse_loss|l1_loss|cxe_loss]
+                              [--soft-labeling]       # the model was trained with FEW_SHOT.SOFT_LABELING (needed for l1_loss / cxe_loss)
     python examples/detect.py --checkpoint model_0930.pth --shared-backbone --no-supp-roialign      # the 0930 model
 
   * weights: a reference `.pth` (utils/checkpoint.py format), a Detectron ResNet `.pkl` for the backbones, or — there is no
@@ -32,7 +33,10 @@ def main():
     ap.add_argument("--first-stage-only", action="store_true")
     ap.add_argument("--shared-backbone", action="store_true", help="one backbone for target and query (SIAMESE_BACKBONE False)")
     ap.add_argument("--no-supp-roialign", action="store_true", help="pool the query pyramid by global average (SUPP_ROIALIGN False)")
-    ap.add_argument("--box-cls-loss", default=spec.BOX_CLS_LOSS, choices=list(spec.BOX_CLS_LOSSES),
+    ap.add_argument("--soft-labeling", action="store_true",
+                    help="the model was trained with IoU soft labels (FEW_SHOT.SOFT_LABELING): admits l1_loss (scored like mse_loss) "
+                         "and cxe_loss (scored like ce_loss)")
+    ap.add_argument("--box-cls-loss", default=spec.BOX_CLS_LOSS, choices=list(spec.BOX_CLS_LOSSES + spec.BOX_CLS_LOSSES_SOFT),
                     help="second-stage classification loss the model was trained with (FEW_SHOT.SECOND_STAGE_CLS_LOSS): "
                          "the sigmoid losses have one class logit and a sigmoid score")
     args = ap.parse_args()
@@ -40,11 +44,11 @@ def main():
     roialign = not args.no_supp_roialign
     if args.checkpoint:
         siamese = checkpoint.has_query_backbone(args.checkpoint)       # the file's own mode
-    shapes = spec.hot_path_shapes(siamese) if args.first_stage_only else spec.full_model_shapes(siamese, box_cls_loss=args.box_cls_loss)
+    shapes = spec.hot_path_shapes(siamese) if args.first_stage_only else spec.full_model_shapes(siamese, box_cls_loss=args.box_cls_loss, soft_labeling=args.soft_labeling)
     defaults = {k: torch.from_numpy(v) for k, v in synth.make_state_dict(shapes).items()}
     if args.checkpoint:
         sd, extras = checkpoint.load_checkpoint(args.checkpoint, defaults=defaults, siamese_backbone=siamese,
-                                                box_cls_loss=args.box_cls_loss)
+                                                box_cls_loss=args.box_cls_loss, soft_labeling=args.soft_labeling)
         print("loaded", args.checkpoint, "(%s backbone)" % ("siamese" if siamese else "shared"),
               {k: v for k, v in extras.items() if not isinstance(v, dict)})
         if "box_cls_loss" in extras and str(extras["box_cls_loss"]) != args.box_cls_loss and not args.first_stage_only:
@@ -54,13 +58,14 @@ def main():
             raise SystemExit("%s was trained with supp_roialign=%r: %s --no-supp-roialign" % (
                 args.checkpoint, bool(extras["supp_roialign"]), "drop" if roialign is False else "add"))
     elif args.c2:
-        sd = checkpoint.load_c2_resnet(args.c2, defaults, siamese_backbone=siamese, box_cls_loss=args.box_cls_loss)
+        sd = checkpoint.load_c2_resnet(args.c2, defaults, siamese_backbone=siamese, box_cls_loss=args.box_cls_loss,
+                                       soft_labeling=args.soft_labeling)
         print("backbones initialised from", args.c2)
     else:
         sd = defaults
         print("synthetic weights (no checkpoint given)")
     det = modules.OneShotDetector(sd, dtype=torch.bfloat16 if args.dtype == "bf16" else torch.float32, siamese_backbone=siamese,
-                                  supp_roialign=roialign, box_cls_loss=args.box_cls_loss)
+                                  supp_roialign=roialign, box_cls_loss=args.box_cls_loss, soft_labeling=args.soft_labeling)
     # two targets and two queries of different sizes
     targets = [torch.from_numpy(synth.make_images("ex.t%d" % i, 1, h, w)[0]) for i, (h, w) in enumerate([(480, 640), (512, 384)])]
     queries = [torch.from_numpy(synth.make_images("ex.q%d" % i, 1, h, w)[0]) for i, (h, w) in enumerate([(127, 127), (96, 160)])]

@@ -6,7 +6,9 @@ RyanXLi/OneshotDet drive it (both stages, SGD with the reference's parameter gro
                              [--no-supp-roialign]       # the query pyramid pooled by global average (SUPP_ROIALIGN False)
                              [--no-center-sample]       # positives inside the whole box (FCOS.CENTER_SAMPLE False)
                              [--loc-loss-type giou|iou|linear_iou]      # the regression loss (FCOS.LOC_LOSS_TYPE)
-                             [--box-cls-loss ce_loss|focal_loss|mse_loss]   # the second stage's classification loss
+                             [--box-cls-loss ce_loss|focal_loss|mse_loss|l1_loss|cxe_loss]   # the second stage's classification loss
+                             [--soft-labeling] [--soft-labeling-func discrete|linear|transLinear|trans4thLinear]   # IoU soft labels
+                                                        # (FEW_SHOT.SOFT_LABELING): mse_loss is held against them, l1_loss / cxe_loss need them
     python examples/train.py --no-center-sample --loc-loss-type iou ...    # the loss of the reference's defaults (defaults.py:309-311)
     python examples/train.py --shared-backbone --no-supp-roialign ...      # the 0930 model (configs/fcos/0930fixed_thres.yaml)
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 examples/train.py ...      # one rank per GPU
@@ -64,28 +66,37 @@ def main():
     ap.add_argument("--no-center-sample", action="store_true", help="positives inside the whole box (FCOS.CENTER_SAMPLE False)")
     ap.add_argument("--loc-loss-type", default=spec.LOC_LOSS_TYPE, choices=list(spec.LOC_LOSS_TYPES),
                     help="regression loss (FCOS.LOC_LOSS_TYPE): 1 - giou, -log(iou) or 1 - iou")
-    ap.add_argument("--box-cls-loss", default=spec.BOX_CLS_LOSS, choices=list(spec.BOX_CLS_LOSSES),
-                    help="second-stage classification loss (FEW_SHOT.SECOND_STAGE_CLS_LOSS); the sigmoid losses have one class logit")
+    ap.add_argument("--box-cls-loss", default=spec.BOX_CLS_LOSS, choices=list(spec.BOX_CLS_LOSSES + spec.BOX_CLS_LOSSES_SOFT),
+                    help="second-stage classification loss (FEW_SHOT.SECOND_STAGE_CLS_LOSS); the sigmoid losses have one class logit; "
+                         "l1_loss / cxe_loss need --soft-labeling")
+    ap.add_argument("--soft-labeling", action="store_true", help="IoU soft labels for the second stage (FEW_SHOT.SOFT_LABELING)")
+    ap.add_argument("--soft-labeling-func", default=spec.SOFT_LABELING_FUNC, choices=list(spec.SOFT_LABELING_FUNCS),
+                    help="soft label as a function of the IoU (FEW_SHOT.SOFT_LABELING_FUNC)")
     args = ap.parse_args()
+    if not args.first_stage_only:
+        spec.box_cls_loss_mode(args.box_cls_loss, soft_labeling=args.soft_labeling)      # l1_loss / cxe_loss without --soft-labeling: refused here
     siamese = not args.shared_backbone
     roialign = not args.no_supp_roialign
     center_sample = not args.no_center_sample
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
     dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float32
-    shapes = spec.hot_path_shapes(siamese) if args.first_stage_only else spec.full_model_shapes(siamese, box_cls_loss=args.box_cls_loss)
+    shapes = spec.hot_path_shapes(siamese) if args.first_stage_only else spec.full_model_shapes(siamese, box_cls_loss=args.box_cls_loss, soft_labeling=args.soft_labeling)
 
     def make_engine(sd):
         return train.TrainEngine(sd, dtype=dtype, lr=0.0005, second_stage=not args.first_stage_only, siamese_backbone=siamese,
                                  supp_roialign=roialign, center_sample=center_sample, loc_loss_type=args.loc_loss_type,
-                                 box_cls_loss=args.box_cls_loss)
+                                 box_cls_loss=args.box_cls_loss, soft_labeling=args.soft_labeling,
+                                 soft_labeling_func=args.soft_labeling_func)
     start = 0
     last = os.path.join(args.out, "last_checkpoint")
     if args.resume and os.path.exists(last):
         eng, start = checkpoint.resume_training(open(last).read().strip(), make_engine, siamese_backbone=siamese,
                                                 supp_roialign=roialign, center_sample=center_sample,
                                                 loc_loss_type=args.loc_loss_type,
-                                                box_cls_loss=None if args.first_stage_only else args.box_cls_loss)
+                                                box_cls_loss=None if args.first_stage_only else args.box_cls_loss,
+                                                soft_labeling=None if args.first_stage_only else args.soft_labeling,
+                                                soft_labeling_func=None if args.first_stage_only else args.soft_labeling_func)
         print("resumed at iteration", start)
     else:
         eng = make_engine(synth.make_state_dict(shapes))      # or checkpoint.load_checkpoint / load_c2_resnet, see detect.py

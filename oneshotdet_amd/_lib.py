@@ -136,6 +136,14 @@ SIGNATURES_BOX_MODES = {
     "osd_box_decode_opt": (_i, [_p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _f, _f, _p, _f, _i, _i, _p]),
 }
 
+# include/oneshotdet_hip_soft_labels.h: the second stage's IoU soft labels (FEW_SHOT.SOFT_LABELING), a third table
+BOX_CLS_L1, BOX_CLS_CXE = 3, 4
+SOFT_LABEL_DISCRETE, SOFT_LABEL_LINEAR, SOFT_LABEL_TRANS_LINEAR, SOFT_LABEL_TRANS_4TH_LINEAR = 0, 1, 2, 3
+SIGNATURES_SOFT_LABELS = {
+    "osd_box_match_sample_soft": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p, _p, _p]),
+    "osd_box_loss_soft": (_i, [_p, _p, _p, _p, _i, _i, _i, _f, _f, _p, _p, _i, _i, _p, _i, _p]),
+}
+
 _lib = None
 
 
@@ -154,7 +162,7 @@ def load():
                        "__graft_entry__.build(); there is no CPU/eager fallback" % LIB_PATH)
     import torch  # noqa: F401  (loads libamdhip64 first)
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_BOX_MODES.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_BOX_MODES.items()) + list(SIGNATURES_SOFT_LABELS.items()):
         fn = getattr(lib, name)   # AttributeError if the symbol is missing
         fn.restype = res
         fn.argtypes = args

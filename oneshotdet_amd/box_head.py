@@ -23,9 +23,10 @@ from .ops import ACT_NONE, ACT_RELU, PackedConv
 class BoxHeadWeights(object):
     """Packed `roi_heads.box.*` (spec.box_head_shapes)."""
 
-    def __init__(self, sd, dtype, prefix="roi_heads.box.", box_cls_loss="ce_loss"):
-        self.box_cls_loss = spec.box_cls_loss_mode(box_cls_loss)
-        spec.check_box_cls_score(sd, self.box_cls_loss, prefix)      # a 1-row cls_score must never be read as two logits
+    def __init__(self, sd, dtype, prefix="roi_heads.box.", box_cls_loss="ce_loss", soft_labeling=False):
+        self.soft_labeling = bool(soft_labeling)
+        self.box_cls_loss = spec.box_cls_loss_mode(box_cls_loss, soft_labeling=self.soft_labeling)
+        spec.check_box_cls_score(sd, self.box_cls_loss, prefix, soft_labeling=self.soft_labeling)      # a 1-row cls_score must never be read as two logits
         c = spec.FPN_OUT
         w0, b0 = sd[prefix + "compress_dim_conv.0.weight"], sd[prefix + "compress_dim_conv.0.bias"]
         self.conv0_x = ops.pack_conv(w0[:, :c].contiguous(), bias=None, dtype=dtype)          # ROI half, no bias
@@ -53,7 +54,7 @@ def check_shots(box_cls_loss, shots):
     """Inference with several queries per image exists for 'ce_loss' only: in the one-logit modes the reference's arg-max over
     shots builds a 4-column index ([M, 1] logits) for the 8 regression columns and raises IndexError (box_head.py:246-253).
     Training is unaffected: it uses the first query only (box_head.py:123-203)."""
-    if shots > 1 and box_cls_loss != "ce_loss":
+    if shots > 1 and box_cls_loss not in ("ce_loss", "cxe_loss"):          # 'cxe_loss' has two logits: it scores and decodes as 'ce_loss'
         raise ValueError("box_cls_loss=%r with %d shots: the reference's arg-max over shots indexes the 8 regression columns of a "
                          "one-logit predictor with a 4-column index and raises IndexError (box_head.py:246-253); the second stage "
                          "detects with one shot in this mode" % (box_cls_loss, shots))
@@ -106,7 +107,7 @@ def run_box_head(bw, feats, qfeats, q_size, boxes, counts, img_h, img_w, shots=1
         t = ops.conv2d(t, bw.fc7, act=ACT_RELU)
         ops.conv2d(t, bw.pred, act=ACT_NONE, out=preds[s].view(n * r, 1, 1, -1))
     dec = ops.box_decode(preds, boxes, counts, spec.BOX_REG_WEIGHTS, img_h, img_w, spec.BOX_SCORE_THRESH, want_raw=want_raw,
-                         img_hw=img_hw, cls_loss=bw.box_cls_loss)
+                         img_hw=img_hw, cls_loss=bw.box_cls_loss, soft_labeling=bw.soft_labeling)
     scores, dboxes = dec[0], dec[1]
     bs, ss, _, cnt = ops.rank_sort_gather(scores, dboxes, r)
     keep = min(spec.BOX_DETECTIONS_PER_IMG, r)

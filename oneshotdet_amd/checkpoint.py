@@ -16,6 +16,9 @@ options center_sample / loc_loss_type (FCOS.CENTER_SAMPLE / FCOS.LOC_LOSS_TYPE):
 box_cls_loss (FEW_SHOT.SECOND_STAGE_CLS_LOSS) changes a SHAPE: `roi_heads.box.predictor.cls_score.*` has 2 rows for 'ce_loss' and
 1 for 'focal_loss' / 'mse_loss'.  Loading checks the shapes of the mode it is given; the two one-row modes share their shapes, so
 training checkpoints record the mode and `resume_training` refuses to continue a run on the other loss.
+soft_labeling / soft_labeling_func (FEW_SHOT.SOFT_LABELING / SOFT_LABELING_FUNC) change no key and no shape by themselves ('l1_loss'
+has 'mse_loss's shapes, 'cxe_loss' has 'ce_loss's): training checkpoints record both, a file without the fields was trained with
+(False, "linear"), and `resume_training` refuses a mismatch.
 """
 import os
 import pickle
@@ -75,17 +78,18 @@ def has_query_backbone(path_or_sd):
     return any(k.startswith("supp_backbone.") for k in strip_prefix_if_present(sd))
 
 
-def load_checkpoint(path, second_stage=None, defaults=None, siamese_backbone=True, box_cls_loss="ce_loss"):
+def load_checkpoint(path, second_stage=None, defaults=None, siamese_backbone=True, box_cls_loss="ce_loss", soft_labeling=False):
     """Read a reference `.pth` (or a bare state_dict file) -> (state_dict under the reference's key names, extras).
     second_stage: True = require roi_heads.box.*, False = first stage only, None = take it when present.
     defaults: values for keys the file lacks (utils/checkpoint.py:107-115 keeps the model's own initialisation for
     FEW_SHOT.UNLOAD_KEYWORD modules); without it a missing key is an error.
     siamese_backbone=False: read the shared-backbone model's keys only (any `supp_backbone.*` in the file is ignored).
-    box_cls_loss: the second stage's classification loss the file was trained with (the shape of its cls_score)."""
+    box_cls_loss: the second stage's classification loss the file was trained with (the shape of its cls_score); 'l1_loss' /
+    'cxe_loss' with soft_labeling=True."""
     data = _read(path)
     loaded = data.pop("model")
     shapes = spec.hot_path_shapes(siamese_backbone)
-    box = spec.box_head_shapes(box_cls_loss=box_cls_loss)
+    box = spec.box_head_shapes(box_cls_loss=box_cls_loss, soft_labeling=soft_labeling)
     probe = strip_prefix_if_present(loaded)
     has_box = any(k.endswith("box.fc6.weight") for k in probe)
     if second_stage or (second_stage is None and has_box):
@@ -118,13 +122,16 @@ def save_training_checkpoint(path, engine, iteration, tag_last=True):
     `optimizer` holds TrainEngine.optimizer_state_dict() (momentum buffers under reference names, steps taken, lr);
     `siamese_backbone` the engine's mode (a shared engine writes no `supp_backbone.*`); `supp_roialign` its query pooling (the
     only record of it: the pooling has no weights); `center_sample` / `loc_loss_type` the FCOS loss it trained with (likewise);
-    `box_cls_loss` the second stage's classification loss (the two one-logit losses have the same shapes)."""
+    `box_cls_loss` the second stage's classification loss (the two one-logit losses have the same shapes); `soft_labeling` /
+    `soft_labeling_func` the soft labels it was held against (no weights either)."""
     return save_checkpoint(path, engine.state_dict(), tag_last=tag_last, optimizer=engine.optimizer_state_dict(),
                            iteration=int(iteration), siamese_backbone=bool(getattr(engine, "siamese_backbone", True)),
                            supp_roialign=bool(getattr(engine, "supp_roialign", True)),
                            center_sample=bool(getattr(engine, "center_sample", spec.CENTER_SAMPLE)),
                            loc_loss_type=str(getattr(engine, "loc_loss_type", spec.LOC_LOSS_TYPE)),
-                           box_cls_loss=str(getattr(engine, "box_cls_loss", spec.BOX_CLS_LOSS)))
+                           box_cls_loss=str(getattr(engine, "box_cls_loss", spec.BOX_CLS_LOSS)),
+                           soft_labeling=bool(getattr(engine, "soft_labeling", spec.SOFT_LABELING)),
+                           soft_labeling_func=str(getattr(engine, "soft_labeling_func", spec.SOFT_LABELING_FUNC)))
 
 
 def _loss_name(mode):
@@ -133,7 +140,7 @@ def _loss_name(mode):
 
 
 def resume_training(path, make_engine, siamese_backbone=None, supp_roialign=None, center_sample=None, loc_loss_type=None,
-                    box_cls_loss=None):
+                    box_cls_loss=None, soft_labeling=None, soft_labeling_func=None):
     """Load a checkpoint written by save_training_checkpoint: make_engine(state_dict) -> TrainEngine; its momentum and
     step count are restored.  Returns (engine, iteration).  The file's mode (recorded by save_training_checkpoint; for
     older files: whether it holds `supp_backbone.*`) must be the engine's: a resumed run never ties or unties weights
@@ -142,11 +149,22 @@ def resume_training(path, make_engine, siamese_backbone=None, supp_roialign=None
     files written before the option existed) must match it and the engine's.  And for the FCOS loss: center_sample /
     loc_loss_type are the caller's expectations (None: whatever the file holds), a file without the fields was trained with
     (True, "giou"), the only loss there was.  And for the second stage's classification loss: box_cls_loss is the caller's
-    expectation (None: whatever the file holds), a file without the field was trained with "ce_loss"."""
+    expectation (None: whatever the file holds), a file without the field was trained with "ce_loss".  And for the soft labels:
+    soft_labeling / soft_labeling_func are the caller's expectations (None: whatever the file holds), a file without the fields was
+    trained with (False, "linear"); the function only matters where soft labels are on."""
     data = _read(path)
+    soft = (data.get("soft_labeling"), data.get("soft_labeling_func"))
+    soft = spec.soft_labeling_mode(spec.SOFT_LABELING if soft[0] is None else bool(soft[0]),
+                                   spec.SOFT_LABELING_FUNC if soft[1] is None else str(soft[1]))
+    want_soft = spec.soft_labeling_mode(soft[0] if soft_labeling is None else soft_labeling,
+                                        soft[1] if soft_labeling_func is None else soft_labeling_func)
+    if want_soft[0] != soft[0] or (soft[0] and want_soft[1] != soft[1]):
+        raise ValueError("%s was trained with soft_labeling=%r, soft_labeling_func=%r; resuming it with soft_labeling=%r, "
+                         "soft_labeling_func=%r would continue the run on other labels: build the engine with soft_labeling=%r, "
+                         "soft_labeling_func=%r" % (path, soft[0], soft[1], want_soft[0], want_soft[1], soft[0], soft[1]))
     box = data.get("box_cls_loss")
-    box = spec.BOX_CLS_LOSS if box is None else spec.box_cls_loss_mode(str(box))
-    if box_cls_loss is not None and spec.box_cls_loss_mode(box_cls_loss) != box:
+    box = spec.BOX_CLS_LOSS if box is None else spec.box_cls_loss_mode(str(box), soft_labeling=soft[0])
+    if box_cls_loss is not None and spec.box_cls_loss_mode(box_cls_loss, soft_labeling=soft[0]) != box:
         raise ValueError("%s was trained with box_cls_loss=%r; resuming it with box_cls_loss=%r would continue the run on another "
                          "objective: build the engine with box_cls_loss=%r" % (path, box, box_cls_loss, box))
     loss = (data.get("center_sample"), data.get("loc_loss_type"))
@@ -167,8 +185,12 @@ def resume_training(path, make_engine, siamese_backbone=None, supp_roialign=None
                          "load_checkpoint(..., siamese_backbone=%r) into a fresh run instead"
                          % (path, _MODE[mode], _MODE[bool(siamese_backbone)], "untie" if siamese_backbone else "tie",
                             bool(siamese_backbone)))
-    sd, extras = load_checkpoint(path, siamese_backbone=mode, box_cls_loss=box)
+    sd, extras = load_checkpoint(path, siamese_backbone=mode, box_cls_loss=box, soft_labeling=soft[0])
     eng = make_engine(sd)
+    built_soft = (bool(getattr(eng, "soft_labeling", spec.SOFT_LABELING)), str(getattr(eng, "soft_labeling_func", spec.SOFT_LABELING_FUNC)))
+    if built_soft[0] != soft[0] or (soft[0] and built_soft[1] != soft[1]):
+        raise ValueError("%s was trained with soft_labeling=%r, soft_labeling_func=%r but make_engine built an engine with "
+                         "soft_labeling=%r, soft_labeling_func=%r" % (path, soft[0], soft[1], built_soft[0], built_soft[1]))
     built_box = str(getattr(eng, "box_cls_loss", spec.BOX_CLS_LOSS))
     if built_box != box:
         raise ValueError("%s was trained with box_cls_loss=%r but make_engine built an engine with box_cls_loss=%r"
@@ -228,7 +250,7 @@ def translate_c2_resnet_name(name):
     return None if leaf is None else "layer%d.%d.%s.%s" % (stage - 1, block, conv, leaf)
 
 
-def load_c2_resnet(path, defaults, second_stage=None, siamese_backbone=True, box_cls_loss="ce_loss"):
+def load_c2_resnet(path, defaults, second_stage=None, siamese_backbone=True, box_cls_loss="ce_loss", soft_labeling=False):
     """A Detectron ResNet `.pkl` (dict of numpy blobs, optionally under "blobs"; pickled by Python 2: latin1) -> a full
     state_dict: the ResNet bodies of BOTH backbones come from the file, every other entry (FrozenBN running statistics —
     AffineChannel has none —, FPN, FCOS head, second stage) from `defaults`, as `DetectronCheckpointer.load` leaves the
@@ -243,7 +265,7 @@ def load_c2_resnet(path, defaults, second_stage=None, siamese_backbone=True, box
             loaded[name] = torch.as_tensor(blobs[k])
     shapes = spec.hot_path_shapes(siamese_backbone)
     if second_stage or (second_stage is None and all(k in defaults for k in spec.box_head_shapes())):
-        shapes.update(spec.box_head_shapes(box_cls_loss=box_cls_loss))
+        shapes.update(spec.box_head_shapes(box_cls_loss=box_cls_loss, soft_labeling=soft_labeling))
     body = OrderedDict((k, v) for k, v in shapes.items() if ".body." in k and not k.endswith(("running_mean", "running_var")))
     sd, missing = align_state_dict(body, loaded)
     if missing:

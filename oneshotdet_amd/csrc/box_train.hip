@@ -10,6 +10,7 @@
 // The convolutions / fully connected layers run forward, data gradient and weight gradient on the implicit-GEMM kernels.
 #include "osd_common.h"
 #include "../../include/oneshotdet_hip_box_modes.h"
+#include "../../include/oneshotdet_hip_soft_labels.h"
 
 namespace {
 
@@ -25,17 +26,39 @@ __device__ __forceinline__ float iou_plus1(const float* a, const float* b) {
   return __fdiv_rn(inter, __fsub_rn(__fadd_rn(area_a, area_b), inter));
 }
 
+// FastRCNNLossComputation.soft_labeling_function (box_head/loss.py:81-104) of t = the IoU with the matched ground truth, float32 in
+// the reference's operation order, contraction off; the comparisons are against the float32 values of 0.5 and 0.1 (a float32 tensor
+// compared with a Python scalar).  (2t)^4 is two squarings: within 2 ulp of the reference's pow.
+__device__ __forceinline__ float soft_label(float t, int func) {
+  const float ge5 = t >= 0.5f ? 1.f : 0.f;
+  if (func == OSD_SOFT_LABEL_DISCRETE) return ge5;
+  if (func == OSD_SOFT_LABEL_LINEAR) return t;
+  const float upper = __fmul_rn(__fadd_rn(__fmul_rn(0.2f, t), 0.8f), ge5);
+  const float lt5 = t < 0.5f ? 1.f : 0.f;
+  if (func == OSD_SOFT_LABEL_TRANS_LINEAR) {
+    const float middle = __fmul_rn(__fmul_rn(__fsub_rn(__fmul_rn(2.25f, t), 0.225f), t >= 0.1f ? 1.f : 0.f), lt5);
+    return __fadd_rn(__fadd_rn(upper, middle), 0.f);
+  }
+  const float x = __fmul_rn(2.f, t);
+  const float x2 = __fmul_rn(x, x);
+  return __fadd_rn(upper, __fmul_rn(__fmul_rn(0.9f, __fmul_rn(x2, x2)), lt5));
+}
+
 // One workgroup per image.  labels: -1 ignored (past the count), 0 background (best IoU < thresh), else the matched
 // ground truth's label (IoU >= thresh: high == low threshold, allow_low_quality_matches False).  Sampling: the positives
 // / negatives with the smallest keys (ties: lower index), at most num_pos_max positives and `batch` in all — a uniformly
 // random subset when the keys are uniform randoms, i.e. positive[randperm(n)[:k]] with randperm = argsort(keys).
 // The sampled rows come out in ascending proposal order (torch.nonzero(pos | neg), loss.py:292).
-__global__ void __launch_bounds__(1024) box_match_sample_kernel(
+// SOFT (FEW_SHOT.SOFT_LABELING, include/oneshotdet_hip_soft_labels.h): every sampled row also gets its soft label
+// soft_label(IoU with the matched ground truth) in s_soft (0 for background rows and rows past the count), every proposal in all_soft.
+template <bool SOFT>
+__device__ __forceinline__ void box_match_sample_body(
     const float* __restrict__ boxes, const int32_t* __restrict__ counts, const float* __restrict__ gt,
     const int32_t* __restrict__ gt_count, const int32_t* __restrict__ gt_labels, const float* __restrict__ keys, int P, int G,
     int batch, int num_pos_max, float thresh, float wx, float wy, float ww, float wh, float* __restrict__ s_boxes,
     int32_t* __restrict__ s_labels, float* __restrict__ s_targets, int32_t* __restrict__ s_index, int32_t* __restrict__ s_count,
-    int32_t* __restrict__ all_labels, int32_t* __restrict__ all_matched) {
+    int32_t* __restrict__ all_labels, int32_t* __restrict__ all_matched, int soft_func, float* __restrict__ s_soft,
+    float* __restrict__ all_soft) {
   __shared__ int lab[kMaxProps];
   __shared__ float keyv[kMaxProps];
   __shared__ int part[1024];
@@ -50,6 +73,7 @@ __global__ void __launch_bounds__(1024) box_match_sample_kernel(
   int npos = 0, nneg = 0;
   for (int i = t; i < P; i += 1024) {
     int l = -1, m = -1;
+    [[maybe_unused]] float sv = 0.f;                        // match_iou[matched_idxs < 0] = 0 (loss.py:61-62), then f(0) = 0
     if (i < cnt && ng > 0) {
       float best = -1.f;
       int arg = 0;
@@ -59,6 +83,10 @@ __global__ void __launch_bounds__(1024) box_match_sample_kernel(
       }
       if (best < thresh) { l = 0; m = -1; }                 // Matcher.BELOW_LOW_THRESHOLD
       else { l = gt_labels ? gt_labels[(size_t)img * G + arg] : 1; m = arg; }
+      if constexpr (SOFT) sv = l >= 1 ? soft_label(best, soft_func) : 0.f;
+    }
+    if constexpr (SOFT) {
+      if (all_soft) all_soft[(size_t)img * P + i] = sv;
     }
     lab[i] = l;
     keyv[i] = keys[(size_t)img * P + i];
@@ -184,13 +212,16 @@ __global__ void __launch_bounds__(1024) box_match_sample_kernel(
       const int l = lab[i];
       // matched_targets = target[matched_idxs.clamp(min=0)] (loss.py:70): background rows are encoded against box 0
       int m = 0;
+      [[maybe_unused]] float sv = 0.f;                      // background rows: 0
       if (l >= 1) {
         float best = -1.f;
         for (int g = 0; g < ng; ++g) {
           const float v = iou_plus1(gb + g * 4, b);
           if (v > best) { best = v; m = g; }
         }
+        if constexpr (SOFT) sv = soft_label(best, soft_func);
       }
+      if constexpr (SOFT) s_soft[row] = sv;
       const float* r = gb + m * 4;
       // BoxCoder.encode (box_coder.py:21-50), float32 in its order
       const float ew = __fadd_rn(__fsub_rn(b[2], b[0]), 1.f), eh = __fadd_rn(__fsub_rn(b[3], b[1]), 1.f);
@@ -216,8 +247,31 @@ __global__ void __launch_bounds__(1024) box_match_sample_kernel(
     for (int q = 0; q < 4; ++q) { s_boxes[row * 4 + q] = 0.f; s_targets[row * 4 + q] = 0.f; }
     s_labels[row] = -1;
     s_index[row] = -1;
+    if constexpr (SOFT) s_soft[row] = 0.f;
   }
   if (t == 0) s_count[img] = kept;
+}
+
+// the config of record (no soft labels): the launch osd_box_match_sample has always made
+__global__ void __launch_bounds__(1024) box_match_sample_kernel(
+    const float* __restrict__ boxes, const int32_t* __restrict__ counts, const float* __restrict__ gt,
+    const int32_t* __restrict__ gt_count, const int32_t* __restrict__ gt_labels, const float* __restrict__ keys, int P, int G,
+    int batch, int num_pos_max, float thresh, float wx, float wy, float ww, float wh, float* __restrict__ s_boxes,
+    int32_t* __restrict__ s_labels, float* __restrict__ s_targets, int32_t* __restrict__ s_index, int32_t* __restrict__ s_count,
+    int32_t* __restrict__ all_labels, int32_t* __restrict__ all_matched) {
+  box_match_sample_body<false>(boxes, counts, gt, gt_count, gt_labels, keys, P, G, batch, num_pos_max, thresh, wx, wy, ww, wh, s_boxes,
+                               s_labels, s_targets, s_index, s_count, all_labels, all_matched, 0, nullptr, nullptr);
+}
+
+__global__ void __launch_bounds__(1024) box_match_sample_soft_kernel(
+    const float* __restrict__ boxes, const int32_t* __restrict__ counts, const float* __restrict__ gt,
+    const int32_t* __restrict__ gt_count, const int32_t* __restrict__ gt_labels, const float* __restrict__ keys, int P, int G,
+    int batch, int num_pos_max, float thresh, float wx, float wy, float ww, float wh, float* __restrict__ s_boxes,
+    int32_t* __restrict__ s_labels, float* __restrict__ s_targets, int32_t* __restrict__ s_index, int32_t* __restrict__ s_count,
+    int32_t* __restrict__ all_labels, int32_t* __restrict__ all_matched, int soft_func, float* __restrict__ s_soft,
+    float* __restrict__ all_soft) {
+  box_match_sample_body<true>(boxes, counts, gt, gt_count, gt_labels, keys, P, G, batch, num_pos_max, thresh, wx, wy, ww, wh, s_boxes,
+                              s_labels, s_targets, s_index, s_count, all_labels, all_matched, soft_func, s_soft, all_soft);
 }
 
 // Sigmoid focal loss of one logit and its derivative in the reference's CUDA form (csrc/cuda/SigmoidFocalLoss_cuda.cu:21-101, one
@@ -244,13 +298,24 @@ __device__ __forceinline__ float box_focal_grad(float x, int label, float gamma,
 //   OSD_BOX_CLS_MSE    L = 1, loss.py:362-363: sigmoid(logits) [M,1] - labels.float() [M] broadcasts to [M,M], so the reference's
 //                      mean runs over M x M pairs: mean_ij (s_i - l_j)^2 = mean_i (s_i - ml)^2 + ml (1 - ml), ml = n_pos / M
 //                      (labels 0 / 1).  Summed in that form: every term is non-negative, nothing cancels.
+// With FEW_SHOT.SOFT_LABELING (include/oneshotdet_hip_soft_labels.h) `soft` holds a row's soft label t in [0, 1]; the hard labels still
+// pick the regression rows:
+//   kBoxClsSoftMse     L = 1, loss.py:360-361: the same [M,M] broadcast against the soft labels: mean_i (s_i - mt)^2 + mean_j (t_j - mt)^2,
+//                      mt = mean(t), reduced first; both sums of non-negative terms
+//   OSD_BOX_CLS_L1     L = 1, loss.py:364-365: mean over the [M,M] broadcast of |s_i - t_j|, which has no closed form: the valid rows'
+//                      soft labels go through LDS in tiles of kL1Tile rows and every thread walks every tile for its rows
+//   OSD_BOX_CLS_CXE    L = 2, loss.py:294-296,366-367: -mean([1 - t, t] * log softmax) over the [M,2] tensor, i.e. over 2M elements
 // The smooth-L1 term, the reduction, the NaN poisoning of labels > 1 and the zeroing of invalid rows are one chain for all modes.
+constexpr int kBoxClsSoftMse = 100;      // OSD_BOX_CLS_MSE of osd_box_loss_soft
+constexpr int kL1Tile = 1024;            // soft labels staged per trip: 4 KB of LDS next to the 8 KB of the reduction
+
 template <typename T, int MODE>
 __device__ __forceinline__ void box_loss_body(const T* __restrict__ pred, const int32_t* __restrict__ labels,
                                               const float* __restrict__ targets, const int32_t* __restrict__ s_count,
                                               int n_img, int S, int pstride, float w_cls, float w_box, float gamma, float alpha,
-                                              float* __restrict__ losses, T* __restrict__ d_pred, int gstride) {
-  constexpr int L = MODE == OSD_BOX_CLS_CE ? 2 : 1;
+                                              float* __restrict__ losses, T* __restrict__ d_pred, int gstride,
+                                              const float* __restrict__ soft = nullptr) {
+  constexpr int L = (MODE == OSD_BOX_CLS_CE || MODE == OSD_BOX_CLS_CXE) ? 2 : 1;
   __shared__ float red[2][1024];
   __shared__ int nval, bad_label, npos_all;
   const int t = threadIdx.x;
@@ -265,7 +330,7 @@ __device__ __forceinline__ void box_loss_body(const T* __restrict__ pred, const 
   const int M = n_img * S;
   const float inv_n = nval > 0 ? 1.f / (float)nval : 0.f;
   float inv_pos = 0.f, ml = 0.f;          // 1 / max(n_pos, 1) (focal); mean label n_pos / valid rows (mse)
-  if constexpr (MODE != OSD_BOX_CLS_CE) {
+  if constexpr (MODE == OSD_BOX_CLS_FOCAL || MODE == OSD_BOX_CLS_MSE) {
     // both normalisers need n_pos before the first gradient is written: count the valid positives first (integers: any order)
     int c = 0;
     for (int r = t; r < M; r += 1024) {
@@ -279,6 +344,22 @@ __device__ __forceinline__ void box_loss_body(const T* __restrict__ pred, const 
     const int n_pos = npos_all;
     inv_pos = 1.f / (float)max(n_pos, 1);
     ml = (float)n_pos * inv_n;
+  }
+  if constexpr (MODE == kBoxClsSoftMse) {
+    // mt = the mean soft label of the valid rows, before the first gradient is written (fixed order: own rows, then the tree)
+    float ts = 0.f;
+    for (int r = t; r < M; r += 1024) {
+      const int img = r / S, ri = r - img * S;
+      if (ri < min(s_count[img], S)) ts += soft[r];
+    }
+    red[0][t] = ts;
+    __syncthreads();
+    for (int s = 512; s > 0; s >>= 1) {
+      if (t < s) red[0][t] += red[0][t + s];
+      __syncthreads();
+    }
+    ml = red[0][0] * inv_n;
+    __syncthreads();                       // red[] is written again below
   }
   float lc = 0.f, lb = 0.f;
   for (int r = t; r < M; r += 1024) {
@@ -308,12 +389,28 @@ __device__ __forceinline__ void box_loss_body(const T* __restrict__ pred, const 
       const float x = to_f32(p[0]);
       lc += box_focal_value(x, l, gamma, alpha);
       if (g) g[0] = from_f32<T>(w_cls * inv_pos * box_focal_grad(x, l, gamma, alpha));
-    } else {
+    } else if constexpr (MODE == OSD_BOX_CLS_MSE) {
       const float s = 1.f / (1.f + expf(-to_f32(p[0])));
       const float d = s - ml;
       lc += d * d;
       if (g) g[0] = from_f32<T>(w_cls * 2.f * inv_n * d * s * (1.f - s));
-    }
+    } else if constexpr (MODE == kBoxClsSoftMse) {
+      const float s = 1.f / (1.f + expf(-to_f32(p[0])));
+      const float d = s - ml, e = soft[r] - ml;
+      lc += d * d + e * e;
+      if (g) g[0] = from_f32<T>(w_cls * 2.f * inv_n * d * s * (1.f - s));
+    } else if constexpr (MODE == OSD_BOX_CLS_CXE) {
+      const float x0 = to_f32(p[0]), x1 = to_f32(p[1]), tl = soft[r];
+      const float m = fmaxf(x0, x1);
+      const float e0 = expf(x0 - m), e1 = expf(x1 - m);
+      const float lse = m + logf(e0 + e1);
+      lc += (1.f - tl) * (lse - x0) + tl * (lse - x1);
+      if (g) {
+        const float s0 = e0 / (e0 + e1), s1 = e1 / (e0 + e1);
+        g[0] = from_f32<T>(w_cls * 0.5f * inv_n * (s0 - (1.f - tl)));
+        g[1] = from_f32<T>(w_cls * 0.5f * inv_n * (s1 - tl));
+      }
+    }                                      // OSD_BOX_CLS_L1: the pair pass below
     if (l >= 1) {
 #pragma unroll
       for (int k = 0; k < 4; ++k) {
@@ -321,6 +418,51 @@ __device__ __forceinline__ void box_loss_body(const T* __restrict__ pred, const 
         const float n = fabsf(d);
         lb += n < 1.f ? 0.5f * n * n : n - 0.5f;                       // smooth_l1_loss(beta = 1), summed
         if (g) g[L + 4 * l + k] = from_f32<T>(w_box * inv_n * (n < 1.f ? d : (d > 0.f ? 1.f : -1.f)));
+      }
+    }
+  }
+  if constexpr (MODE == OSD_BOX_CLS_L1) {
+    // sum_ij |s_i - t_j| over the valid rows i and j, and per row the integer #(t_j < s_i) - #(t_j > s_i) of the gradient
+    // (sign(0) = 0).  A row past its image's count is staged as NaN: it fails both comparisons and its |.| is dropped.
+    __shared__ __attribute__((aligned(16))) float tile[kL1Tile];
+    for (int rb = 0; rb < M; rb += 1024) {                  // uniform trip counts: every thread reaches every barrier
+      const int r = rb + t;
+      bool mine = false;
+      float s = 0.f;
+      if (r < M) {
+        const int img = r / S, ri = r - img * S;
+        mine = ri < min(s_count[img], S) && labels[r] <= 1;
+        if (mine) s = 1.f / (1.f + expf(-to_f32(pred[(size_t)r * pstride])));
+      }
+      float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
+      int sg = 0;
+      for (int tb = 0; tb < M; tb += kL1Tile) {
+        __syncthreads();                                    // the previous trip's readers are done
+        for (int k = t; k < kL1Tile; k += 1024) {
+          const int rr = tb + k;
+          float v = __builtin_nanf("");
+          if (rr < M) {
+            const int img = rr / S, ri = rr - img * S;
+            if (ri < min(s_count[img], S)) v = soft[rr];
+          }
+          tile[k] = v;
+        }
+        __syncthreads();
+        if (mine) {
+          const int lim = min(kL1Tile, M - tb);             // the tile's tail past M holds NaN too: whole groups of four
+          for (int j = 0; j < lim; j += 4) {
+            const f32x4 tj = *reinterpret_cast<const f32x4*>(tile + j);
+            a0 += tj[0] == tj[0] ? fabsf(s - tj[0]) : 0.f;
+            a1 += tj[1] == tj[1] ? fabsf(s - tj[1]) : 0.f;
+            a2 += tj[2] == tj[2] ? fabsf(s - tj[2]) : 0.f;
+            a3 += tj[3] == tj[3] ? fabsf(s - tj[3]) : 0.f;
+            sg += (tj[0] < s) - (tj[0] > s) + (tj[1] < s) - (tj[1] > s) + (tj[2] < s) - (tj[2] > s) + (tj[3] < s) - (tj[3] > s);
+          }
+        }
+      }
+      if (mine) {
+        lc += (a0 + a1) + (a2 + a3);
+        if (d_pred) d_pred[(size_t)r * gstride] = from_f32<T>(w_cls * inv_n * inv_n * s * (1.f - s) * (float)sg);
       }
     }
   }
@@ -337,8 +479,14 @@ __device__ __forceinline__ void box_loss_body(const T* __restrict__ pred, const 
       losses[0] = w_cls * red[0][0] * inv_n + poison;     // 5 * F.cross_entropy(class_logits, labels)
     else if constexpr (MODE == OSD_BOX_CLS_FOCAL)
       losses[0] = w_cls * red[0][0] * inv_pos + poison;   // 5 * SigmoidFocalLoss(...).sum() / max(n_pos, 1)
-    else
+    else if constexpr (MODE == OSD_BOX_CLS_MSE)
       losses[0] = w_cls * (red[0][0] * inv_n + ml * (1.f - ml)) + poison;   // 5 * mean over [M,M] of (sigmoid - labels)^2
+    else if constexpr (MODE == kBoxClsSoftMse)
+      losses[0] = w_cls * red[0][0] * inv_n + poison;                       // 5 * mean over [M,M] of (sigmoid - soft labels)^2
+    else if constexpr (MODE == OSD_BOX_CLS_L1)
+      losses[0] = w_cls * red[0][0] * inv_n * inv_n + poison;               // 5 * mean over [M,M] of |sigmoid - soft labels|
+    else
+      losses[0] = w_cls * red[0][0] * inv_n * 0.5f + poison;                // 5 * CXE: the mean runs over the 2M elements of [M,2]
     losses[1] = w_box * red[1][0] * inv_n + poison;     // 2.5 * smooth_l1(sum) / labels.numel()
     losses[2] = (float)nval;
   }
@@ -361,6 +509,16 @@ __global__ void __launch_bounds__(1024) box_loss_mode_kernel(const T* __restrict
                                                              float alpha, float* __restrict__ losses, T* __restrict__ d_pred,
                                                              int gstride) {
   box_loss_body<T, MODE>(pred, labels, targets, s_count, n_img, S, pstride, w_cls, w_box, gamma, alpha, losses, d_pred, gstride);
+}
+
+// the soft-label modes (osd_box_loss_soft)
+template <typename T, int MODE>
+__global__ void __launch_bounds__(1024) box_loss_soft_kernel(const T* __restrict__ pred, const int32_t* __restrict__ labels,
+                                                             const float* __restrict__ targets, const int32_t* __restrict__ s_count,
+                                                             const float* __restrict__ soft, int n_img, int S, int pstride,
+                                                             float w_cls, float w_box, float* __restrict__ losses,
+                                                             T* __restrict__ d_pred, int gstride) {
+  box_loss_body<T, MODE>(pred, labels, targets, s_count, n_img, S, pstride, w_cls, w_box, 0.f, 0.f, losses, d_pred, gstride, soft);
 }
 
 __device__ __forceinline__ void ld2(const float* p, float& a, float& b) {
@@ -621,6 +779,68 @@ extern "C" int osd_box_match_sample(const float* boxes, const int32_t* counts, c
                      gt_labels, keys, max_props, max_gt, batch_per_image, num_pos, iou_thresh, reg_weights[0], reg_weights[1],
                      reg_weights[2], reg_weights[3], s_boxes, s_labels, s_targets, s_index, s_count, all_labels, all_matched);
   return osd_check_launch("box_match_sample");
+}
+
+extern "C" int osd_box_match_sample_soft(const float* boxes, const int32_t* counts, const float* gt_boxes, const int32_t* gt_count,
+                                         const int32_t* gt_labels, const float* keys, int n, int max_props, int max_gt,
+                                         int batch_per_image, float positive_fraction, float iou_thresh, const float* reg_weights,
+                                         float* s_boxes, int32_t* s_labels, float* s_targets, int32_t* s_index, int32_t* s_count,
+                                         int32_t* all_labels, int32_t* all_matched, int soft_func, float* s_soft, float* all_soft,
+                                         void* stream) {
+  if (!boxes || !gt_boxes || !gt_count || !keys || !reg_weights || !s_boxes || !s_labels || !s_targets || !s_index || !s_count ||
+      !s_soft)
+    return osd_fail(OSD_ERR_INVALID_ARG, "box_match_sample_soft: null argument");
+  if (soft_func < OSD_SOFT_LABEL_DISCRETE || soft_func > OSD_SOFT_LABEL_TRANS_4TH_LINEAR)
+    return osd_fail(OSD_ERR_INVALID_ARG, "box_match_sample_soft: soft_func %d (OSD_SOFT_LABEL_*: 0..3)", soft_func);
+  if (n == 0) return OSD_OK;
+  if (max_props <= 0 || max_props > kMaxProps)
+    return osd_fail(OSD_ERR_UNSUPPORTED, "box_match_sample_soft: 1..%d proposals per image", kMaxProps);
+  if (max_gt <= 0 || batch_per_image <= 0 || batch_per_image > max_props)
+    return osd_fail(OSD_ERR_INVALID_ARG, "box_match_sample_soft: bad sizes");
+  const int num_pos = (int)(batch_per_image * positive_fraction);
+  hipLaunchKernelGGL(box_match_sample_soft_kernel, dim3(n), dim3(1024), 0, OSD_STREAM(stream), boxes, counts, gt_boxes, gt_count,
+                     gt_labels, keys, max_props, max_gt, batch_per_image, num_pos, iou_thresh, reg_weights[0], reg_weights[1],
+                     reg_weights[2], reg_weights[3], s_boxes, s_labels, s_targets, s_index, s_count, all_labels, all_matched,
+                     soft_func, s_soft, all_soft);
+  return osd_check_launch("box_match_sample_soft");
+}
+
+template <typename T>
+static void launch_box_loss_soft(const void* pred, const int32_t* labels, const float* targets, const int32_t* s_count,
+                                 const float* soft, int n, int S, int pstride, float w_cls, float w_box, float* losses, void* d_pred,
+                                 int gstride, int cls_loss, hipStream_t st) {
+  const T* p = (const T*)pred;
+  T* d = (T*)d_pred;
+  if (cls_loss == OSD_BOX_CLS_MSE)
+    hipLaunchKernelGGL((box_loss_soft_kernel<T, kBoxClsSoftMse>), dim3(1), dim3(1024), 0, st, p, labels, targets, s_count, soft, n, S,
+                       pstride, w_cls, w_box, losses, d, gstride);
+  else if (cls_loss == OSD_BOX_CLS_L1)
+    hipLaunchKernelGGL((box_loss_soft_kernel<T, OSD_BOX_CLS_L1>), dim3(1), dim3(1024), 0, st, p, labels, targets, s_count, soft, n, S,
+                       pstride, w_cls, w_box, losses, d, gstride);
+  else
+    hipLaunchKernelGGL((box_loss_soft_kernel<T, OSD_BOX_CLS_CXE>), dim3(1), dim3(1024), 0, st, p, labels, targets, s_count, soft, n, S,
+                       pstride, w_cls, w_box, losses, d, gstride);
+}
+
+extern "C" int osd_box_loss_soft(const void* pred, const int32_t* labels, const float* targets, const int32_t* s_count, int n,
+                                 int rois_per_image, int pred_stride, float w_cls, float w_box, float* losses, void* d_pred,
+                                 int grad_stride, int dtype, const float* soft, int cls_loss, void* stream) {
+  if (cls_loss != OSD_BOX_CLS_MSE && cls_loss != OSD_BOX_CLS_L1 && cls_loss != OSD_BOX_CLS_CXE)
+    return osd_fail(OSD_ERR_INVALID_ARG, "box_loss_soft: cls_loss %d (OSD_BOX_CLS_MSE / _L1 / _CXE read soft labels)", cls_loss);
+  if (!pred || !labels || !targets || !s_count || !losses || !soft)
+    return osd_fail(OSD_ERR_INVALID_ARG, "box_loss_soft: null argument");
+  const int width = (cls_loss == OSD_BOX_CLS_CXE ? 2 : 1) + 8;
+  if (pred_stride < width || (d_pred && grad_stride < width))
+    return osd_fail(OSD_ERR_INVALID_ARG, "box_loss_soft: %d logits + 8 deltas per row", width - 8);
+  if (dtype == OSD_F32)
+    launch_box_loss_soft<float>(pred, labels, targets, s_count, soft, n, rois_per_image, pred_stride, w_cls, w_box, losses, d_pred,
+                                grad_stride, cls_loss, OSD_STREAM(stream));
+  else if (dtype == OSD_BF16)
+    launch_box_loss_soft<__bf16>(pred, labels, targets, s_count, soft, n, rois_per_image, pred_stride, w_cls, w_box, losses, d_pred,
+                                 grad_stride, cls_loss, OSD_STREAM(stream));
+  else
+    return osd_fail(OSD_ERR_INVALID_ARG, "box_loss_soft: bad dtype");
+  return osd_check_launch("box_loss_soft");
 }
 
 template <typename T>

@@ -369,11 +369,15 @@ class HotPathEngine(object):
     by its global average (run_query_pool).  The pooling has no weights: a state_dict does not tell the two apart.
     box_cls_loss (FEW_SHOT.SECOND_STAGE_CLS_LOSS): "ce_loss" = two class logits and a softmax score; "focal_loss" / "mse_loss" = ONE
     logit and a sigmoid score (roi_box_predictors.py:47-50, inference.py:61-69).  A state_dict whose cls_score has the other mode's
-    row count is refused (ValueError naming the option)."""
+    row count is refused (ValueError naming the option).
+    soft_labeling / soft_labeling_func (FEW_SHOT.SOFT_LABELING / SOFT_LABELING_FUNC): how the model was trained; admits "l1_loss"
+    (one logit, scored like "mse_loss") and "cxe_loss" (two logits, scored like "ce_loss", inference.py:61-69).  Detection itself
+    reads no soft label."""
 
     def __init__(self, state_dict, dtype=torch.float32, device="cuda", siamese_backbone=True, supp_roialign=True,
-                 box_cls_loss="ce_loss"):
-        self.box_cls_loss = spec.box_cls_loss_mode(box_cls_loss)              # ValueError before anything is built
+                 box_cls_loss="ce_loss", soft_labeling=False, soft_labeling_func="linear"):
+        self.soft_labeling, self.soft_labeling_func = spec.soft_labeling_mode(soft_labeling, soft_labeling_func)
+        self.box_cls_loss = spec.box_cls_loss_mode(box_cls_loss, soft_labeling=self.soft_labeling)    # ValueError before anything is built
         if not torch.cuda.is_available():
             raise ops._lib.OsdError("HotPathEngine needs an MI355X: no GPU visible and there is no CPU fallback")
         ops._lib.load()
@@ -397,7 +401,7 @@ class HotPathEngine(object):
         self.box_head = None
         if all(k in self.sd for k in spec.box_head_shapes()):
             from .box_head import BoxHeadWeights
-            self.box_head = BoxHeadWeights(self.sd, self.dtype, box_cls_loss=self.box_cls_loss)
+            self.box_head = BoxHeadWeights(self.sd, self.dtype, box_cls_loss=self.box_cls_loss, soft_labeling=self.soft_labeling)
 
     def tune(self, images, queries, second_stage=False):
         """Pick, by measurement on this device, the conv algorithm (kernel generation, ring depth, tile) for every

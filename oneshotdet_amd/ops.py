@@ -1302,11 +1302,13 @@ def groupnorm_act_rois(x, gamma, beta, groups=32, eps=1e-5, slope=0.2, addend=No
     return out
 
 
-def box_decode(pred, rois, counts, reg_weights, img_h, img_w, score_thresh, want_raw=False, img_hw=None, cls_loss="ce_loss"):
+def box_decode(pred, rois, counts, reg_weights, img_h, img_w, score_thresh, want_raw=False, img_hw=None, cls_loss="ce_loss",
+               soft_labeling=False):
     """pred [S, N*R, P] (L logits, then 8 deltas; L = 2 for cls_loss 'ce_loss', 1 for 'focal_loss' / 'mse_loss' whose score is
     sigmoid(logit)), rois [N,R,4] -> scores [N,R] (-1 = dropped), boxes [N,R,4] (+ the selected logits [N*R,L] and deltas [N*R,8]
-    in fp32 when want_raw)."""
-    mode = spec.BOX_CLS_LOSSES.index(spec.box_cls_loss_mode(cls_loss))
+    in fp32 when want_raw).  With soft_labeling, 'cxe_loss' decodes as 'ce_loss' and 'l1_loss' as 'mse_loss' (inference.py:61-69)."""
+    cls_loss = spec.box_cls_decode_mode(cls_loss, soft_labeling)
+    mode = spec.BOX_CLS_LOSSES.index(cls_loss)
     _chk_dev(pred, rois, counts)
     s, m, p = pred.shape
     n, r, _ = rois.shape
@@ -1327,10 +1329,13 @@ def box_decode(pred, rois, counts, reg_weights, img_h, img_w, score_thresh, want
 
 
 def box_match_sample(boxes, counts, gt_boxes, gt_count, keys, batch_per_image, positive_fraction, iou_thresh, reg_weights,
-                     gt_labels=None, want_all=False):
+                     gt_labels=None, want_all=False, soft_func=None):
     """FastRCNNLossComputation.subsample on the device (osd_box_match_sample): boxes [N,P,4] (ground truth appended),
     counts [N], gt_boxes [N,G,4], gt_count [N], keys [N,P] fp32 uniform randoms -> sampled boxes [N,S,4], labels [N,S]
-    int32, regression targets [N,S,4], proposal index [N,S] int32, counts [N] int32 (+ per-proposal labels / matches)."""
+    int32, regression targets [N,S,4], proposal index [N,S] int32, counts [N] int32 (+ per-proposal labels / matches).
+    soft_func (a name of spec.SOFT_LABELING_FUNCS; FEW_SHOT.SOFT_LABELING): osd_box_match_sample_soft, which also returns the sampled
+    rows' soft labels [N,S] fp32 (+ the per-proposal ones [N,P] with want_all), appended to the tuple."""
+    func = None if soft_func is None else spec.SOFT_LABELING_FUNCS.index(spec.soft_labeling_mode(True, soft_func)[1])
     _chk_dev(boxes, counts, gt_boxes, gt_count, keys)
     n, p, _ = boxes.shape
     s = int(batch_per_image)
@@ -1344,6 +1349,14 @@ def box_match_sample(boxes, counts, gt_boxes, gt_count, keys, batch_per_image, p
     am = torch.empty((n, p), device=dev, dtype=torch.int32) if want_all else None
     rw = (C.c_float * 4)(*[float(v) for v in reg_weights])
     assert keys.shape == (n, p) and keys.dtype == torch.float32
+    if func is not None:
+        ss = torch.empty((n, s), device=dev, dtype=torch.float32)
+        as_ = torch.empty((n, p), device=dev, dtype=torch.float32) if want_all else None
+        _lib.call("osd_box_match_sample_soft", _ptr(boxes.contiguous()), _p(counts), _ptr(gt_boxes.contiguous().float()), _p(gt_count),
+                  _p(gt_labels), _ptr(keys.contiguous()), n, p, gt_boxes.shape[1], s, float(positive_fraction), float(iou_thresh),
+                  rw, _p(sb), _p(sl), _p(st), _p(si), _p(sc), _p(al), _p(am), func, _p(ss), _p(as_), _stream())
+        _rec("box_match_sample_soft", boxes=boxes, soft_func=soft_func, soft=ss)       # the soft launches only: the default step's trace is unchanged
+        return (sb, sl, st, si, sc, al, am, ss, as_) if want_all else (sb, sl, st, si, sc, ss)
     _lib.call("osd_box_match_sample", _ptr(boxes.contiguous()), _p(counts), _ptr(gt_boxes.contiguous().float()), _p(gt_count),
               _p(gt_labels), _ptr(keys.contiguous()), n, p, gt_boxes.shape[1], s, float(positive_fraction), float(iou_thresh),
               rw, _p(sb), _p(sl), _p(st), _p(si), _p(sc), _p(al), _p(am), _stream())
@@ -1351,12 +1364,28 @@ def box_match_sample(boxes, counts, gt_boxes, gt_count, keys, batch_per_image, p
 
 
 def box_loss(pred, labels, targets, s_count, n, rois_per_image, w_cls, w_box, grad_stride=0, cls_loss="ce_loss", gamma=None,
-             alpha=None):
+             alpha=None, soft=None):
     """loss.py:306-393 x the weights of box_head.py:193-194.  pred [M, stride] (L logits, then 8 deltas; cls_loss 'ce_loss':
     L = 2, cross-entropy; 'focal_loss': L = 1, sigmoid focal loss (gamma, alpha: spec.LOSS_GAMMA, spec.BOX_LOSS_ALPHA) summed /
     max(positives, 1); 'mse_loss': L = 1, the reference's [M, M]-broadcast mean of (sigmoid - label)^2)
-    -> losses [3] = (classification, box regression, valid rows) and, with grad_stride, d_pred [M, grad_stride]."""
-    mode = spec.BOX_CLS_LOSSES.index(spec.box_cls_loss_mode(cls_loss))
+    -> losses [3] = (classification, box regression, valid rows) and, with grad_stride, d_pred [M, grad_stride].
+    soft [M] fp32 (FEW_SHOT.SOFT_LABELING: the rows' soft labels from box_match_sample(..., soft_func=)): osd_box_loss_soft for
+    'mse_loss' (the same broadcast against the soft labels), 'l1_loss' (L = 1, the [M, M]-broadcast mean of |sigmoid - soft|) and
+    'cxe_loss' (L = 2, the soft cross-entropy averaged over 2M elements); 'ce_loss' / 'focal_loss' never read soft labels and make
+    the launch they make without them."""
+    soft_mode = spec.box_cls_loss_mode(cls_loss, soft_labeling=soft is not None)
+    if soft is not None and spec.box_loss_reads_soft_labels(soft_mode, True):
+        code = {"mse_loss": _lib.BOX_CLS_MSE, "l1_loss": _lib.BOX_CLS_L1, "cxe_loss": _lib.BOX_CLS_CXE}[soft_mode]
+        m = n * rois_per_image
+        pred2 = pred.reshape(m, -1)
+        assert soft.dtype == torch.float32 and soft.numel() == m and soft.is_contiguous()
+        losses = torch.empty((3,), device=pred.device, dtype=torch.float32)
+        d = torch.empty((m, grad_stride), device=pred.device, dtype=pred.dtype) if grad_stride else None
+        _lib.call("osd_box_loss_soft", _p(pred2), _p(labels), _p(targets), _p(s_count), n, rois_per_image, pred2.shape[1],
+                  float(w_cls), float(w_box), _p(losses), _p(d), int(grad_stride), _dt(pred), _p(soft), code, _stream())
+        _rec("box_loss_soft", pred=pred2, soft=soft, cls_loss=soft_mode, losses=losses, d_pred=d)
+        return losses, d
+    mode = spec.BOX_CLS_LOSSES.index(soft_mode)
     m = n * rois_per_image
     pred2 = pred.reshape(m, -1)
     losses = torch.empty((3,), device=pred.device, dtype=torch.float32)

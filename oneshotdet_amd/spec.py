@@ -50,6 +50,10 @@ BOX_POSITIVE_FRACTION = 0.25          # ROI_HEADS.POSITIVE_FRACTION
 BOX_LOSS_WEIGHTS = (5.0, 2.5)         # loss_classifier *= 5; loss_box_reg *= 2.5
 BOX_CLS_LOSS = "ce_loss"               # yaml / defaults.py:511 FEW_SHOT.SECOND_STAGE_CLS_LOSS
 BOX_CLS_LOSSES = ("ce_loss", "focal_loss", "mse_loss")      # index = OSD_BOX_CLS_* of include/oneshotdet_hip_box_modes.h
+SOFT_LABELING = False                  # yaml / defaults.py FEW_SHOT.SOFT_LABELING: IoU soft labels carried through the sampler (box_head/loss.py:52-62)
+SOFT_LABELING_FUNC = "linear"          # FEW_SHOT.SOFT_LABELING_FUNC (box_head/loss.py:81-104)
+SOFT_LABELING_FUNCS = ("discrete", "linear", "transLinear", "trans4thLinear")     # index = OSD_SOFT_LABEL_* of include/oneshotdet_hip_soft_labels.h
+BOX_CLS_LOSSES_SOFT = ("l1_loss", "cxe_loss")     # only with SOFT_LABELING (box_head/loss.py:364-369): OSD_BOX_CLS_L1 / OSD_BOX_CLS_CXE = 3 / 4
 BOX_LOSS_ALPHA = 0.25                 # FEW_SHOT.SECOND_STAGE_LOSS_ALPHA (defaults.py:512); gamma is FCOS.LOSS_GAMMA (box_head/loss.py:40-44)
 LEVEL_MAP_SCALE = 224                 # poolers.py:16 LevelMapper canonical_scale / canonical_level / eps
 LEVEL_MAP_LEVEL = 4
@@ -64,21 +68,45 @@ def loss_mode(center_sample, loc_loss_type):
 
 
 _BOX_CLS_REFUSED = {
-    "l1_loss": "it needs FEW_SHOT.SOFT_LABELING (IoU soft labels carried through the sampler, box_head/loss.py:52-64,364-365)",
-    "cxe_loss": "it needs FEW_SHOT.SOFT_LABELING (IoU soft labels carried through the sampler, box_head/loss.py:52-64,366-367)",
+    "l1_loss": "it needs FEW_SHOT.SOFT_LABELING (IoU soft labels carried through the sampler, box_head/loss.py:52-64,364-365): pass soft_labeling=True",
+    "cxe_loss": "it needs FEW_SHOT.SOFT_LABELING (IoU soft labels carried through the sampler, box_head/loss.py:52-64,366-367): pass soft_labeling=True",
 }
 
 
-def box_cls_loss_mode(box_cls_loss, loss_weighted=False, neg_support=False, method="concat"):
+def soft_labeling_mode(soft_labeling=False, soft_labeling_func="linear"):
+    """-> (bool, str) of FEW_SHOT.SOFT_LABELING / SOFT_LABELING_FUNC; ValueError for a function box_head/loss.py:92-104 does not have."""
+    if soft_labeling_func not in SOFT_LABELING_FUNCS:
+        raise ValueError("soft_labeling_func must be one of %s (FEW_SHOT.SOFT_LABELING_FUNC), not %r"
+                         % (", ".join(SOFT_LABELING_FUNCS), soft_labeling_func))
+    return bool(soft_labeling), str(soft_labeling_func)
+
+
+def box_loss_reads_soft_labels(box_cls_loss, soft_labeling=False):
+    """Whether the loss launch reads the soft labels: 'mse_loss' / 'l1_loss' / 'cxe_loss' with SOFT_LABELING.  'ce_loss' and
+    'focal_loss' compute soft labels in the reference and never read them (box_head/loss.py:343-359): nothing changes for them."""
+    return bool(soft_labeling) and box_cls_loss_mode(box_cls_loss, soft_labeling=True) in ("mse_loss",) + BOX_CLS_LOSSES_SOFT
+
+
+def box_cls_decode_mode(box_cls_loss, soft_labeling=False):
+    """The BOX_CLS_LOSSES name whose decode a mode uses (inference.py:61-69): 'cxe_loss' scores like 'ce_loss' (softmax of two logits),
+    'l1_loss' like 'mse_loss' (sigmoid of one)."""
+    mode = box_cls_loss_mode(box_cls_loss, soft_labeling=soft_labeling)
+    return {"l1_loss": "mse_loss", "cxe_loss": "ce_loss"}.get(mode, mode)
+
+
+def box_cls_loss_mode(box_cls_loss, loss_weighted=False, neg_support=False, method="concat", soft_labeling=False):
     """-> the validated FEW_SHOT.SECOND_STAGE_CLS_LOSS name; ValueError for a loss box_head/loss.py:343-369 does not have and, by
-    name, for what it has that this build does not support: 'l1_loss' / 'cxe_loss', FEW_SHOT.LOSS_WEIGHTED (its reference path
-    calls .cuda() unconditionally, loss.py:349-357: nothing to record it against), negative support and SECOND_STAGE_METHOD 'rn'."""
+    name, for what it has that this build does not support: FEW_SHOT.LOSS_WEIGHTED (its reference path
+    calls .cuda() unconditionally, loss.py:349-357: nothing to record it against), negative support and SECOND_STAGE_METHOD 'rn'.
+    'l1_loss' / 'cxe_loss' exist with soft_labeling=True (FEW_SHOT.SOFT_LABELING) only, as in the reference (loss.py:364-369)."""
     if loss_weighted:
         raise ValueError("FEW_SHOT.LOSS_WEIGHTED is not supported (box_head/loss.py:349-357)")
     if neg_support:
         raise ValueError("FEW_SHOT.NEG_SUPPORT is not supported: the second stage runs without negative support")
     if method != "concat":
         raise ValueError("FEW_SHOT.SECOND_STAGE_METHOD %r is not supported: only 'concat' (not 'rn' or 'matching')" % (method,))
+    if soft_labeling and box_cls_loss in BOX_CLS_LOSSES_SOFT:
+        return str(box_cls_loss)
     if box_cls_loss in _BOX_CLS_REFUSED:
         raise ValueError("box_cls_loss %r is not supported: %s" % (box_cls_loss, _BOX_CLS_REFUSED[box_cls_loss]))
     if box_cls_loss not in BOX_CLS_LOSSES:
@@ -87,16 +115,16 @@ def box_cls_loss_mode(box_cls_loss, loss_weighted=False, neg_support=False, meth
     return str(box_cls_loss)
 
 
-def box_cls_logits(box_cls_loss="ce_loss"):
-    """Outputs of predictor.cls_score = logits at the head of a predictor row (roi_box_predictors.py:47-50,66-68,76-77): 2 for
-    'ce_loss', 1 for the sigmoid losses."""
-    return BOX_NUM_CLASSES if box_cls_loss_mode(box_cls_loss) == "ce_loss" else 1
+def box_cls_logits(box_cls_loss="ce_loss", soft_labeling=False):
+    """Outputs of predictor.cls_score = logits at the head of a predictor row (roi_box_predictors.py:47-50,63-68,76-77): 2 for
+    'ce_loss' and 'cxe_loss', 1 for the sigmoid losses ('focal_loss', 'mse_loss', 'l1_loss')."""
+    return BOX_NUM_CLASSES if box_cls_loss_mode(box_cls_loss, soft_labeling=soft_labeling) in ("ce_loss", "cxe_loss") else 1
 
 
-def check_box_cls_score(sd, box_cls_loss, prefix="roi_heads.box.", who="the engine"):
+def check_box_cls_score(sd, box_cls_loss, prefix="roi_heads.box.", who="the engine", soft_labeling=False):
     """The state_dict's cls_score must have the mode's row count: a 1-row cls_score read as 2 logits (or the reverse) shifts
     every box delta by a column and detects garbage without an error."""
-    want = box_cls_logits(box_cls_loss)
+    want = box_cls_logits(box_cls_loss, soft_labeling)
     for leaf in ("weight", "bias"):
         rows = int(sd[prefix + "predictor.cls_score." + leaf].shape[0])
         if rows != want:
@@ -175,14 +203,15 @@ def fcos_head_shapes(prefix="rpn.head."):
     return out
 
 
-def box_head_shapes(prefix="roi_heads.box.", box_cls_loss="ce_loss"):
+def box_head_shapes(prefix="roi_heads.box.", box_cls_loss="ce_loss", soft_labeling=False):
     """Second-stage few-shot ROI box head keys (modeling/roi_heads/box_head/box_head.py:40-78: compress_dim_conv =
     Sequential(conv1x1, GN, LeakyReLU, conv1x1, GN, LeakyReLU) -> indices 0,1,3,4; feature_aggreg = Sequential(conv3x3,
     GN, LeakyReLU); fc6/fc7 make_fc; roi_box_predictors.py:37-99 FPNPredictor with 2 classes and 2x4 box deltas).
     box_cls_loss (FEW_SHOT.SECOND_STAGE_CLS_LOSS): cls_score has 2 outputs for 'ce_loss' and ONE for 'focal_loss' / 'mse_loss'
-    (roi_box_predictors.py:47-50,66-68,76-77); bbox_pred keeps its 8."""
+    (roi_box_predictors.py:47-50,66-68,76-77); bbox_pred keeps its 8.  soft_labeling (FEW_SHOT.SOFT_LABELING) admits 'l1_loss' (one
+    output) and 'cxe_loss' (two) and changes no shape by itself."""
     out = OrderedDict()
-    n_logits = box_cls_logits(box_cls_loss)
+    n_logits = box_cls_logits(box_cls_loss, soft_labeling)
     c2 = 2 * FPN_OUT
     out[prefix + "compress_dim_conv.0.weight"] = (c2, c2, 1, 1)
     out[prefix + "compress_dim_conv.0.bias"] = (c2,)
@@ -218,11 +247,11 @@ def hot_path_shapes(siamese_backbone=True):
     return out
 
 
-def full_model_shapes(siamese_backbone=True, box_cls_loss="ce_loss"):
+def full_model_shapes(siamese_backbone=True, box_cls_loss="ce_loss", soft_labeling=False):
     """Hot path + second-stage box head = every state_dict entry of the reference model under the config of record
     (siamese_backbone: see hot_path_shapes; box_cls_loss: see box_head_shapes)."""
     out = hot_path_shapes(siamese_backbone)
-    out.update(box_head_shapes(box_cls_loss=box_cls_loss))
+    out.update(box_head_shapes(box_cls_loss=box_cls_loss, soft_labeling=soft_labeling))
     return out
 
 

@@ -28,6 +28,11 @@ locations are positive (True: inside a box's sampling region; False: inside the 
 box_cls_loss (FEW_SHOT.SECOND_STAGE_CLS_LOSS, box_head/loss.py:343-363; second_stage=True only): "ce_loss" (the config of record),
 "focal_loss" or "mse_loss".  The two sigmoid losses have ONE class logit (roi_box_predictors.py:47-50): the predictor conv has 9
 rows instead of 10 and the loss launch is another instantiation of the same kernel body; everything else in the step is the same.
+
+soft_labeling / soft_labeling_func (FEW_SHOT.SOFT_LABELING / SOFT_LABELING_FUNC, box_head/loss.py:52-62,81-104; second_stage=True
+only): every sampled ROI carries soft = f(IoU with its matched ground truth) (0 for background) from the sampler to the loss;
+"mse_loss" is then held against the soft labels, and "l1_loss" (one logit) and "cxe_loss" (two) exist.  "ce_loss" and "focal_loss"
+never read soft labels: with them the step makes the launches it makes without the option.
 """
 import math
 import os
@@ -95,9 +100,10 @@ class TrainEngine(ForwardPass, BackwardPass, SecondStage, Update, State):
     def __init__(self, state_dict, dtype=torch.bfloat16, device="cuda", lr=0.0005, momentum=0.9, weight_decay=0.0001,
                  process_group=None, wgrad_side_stream=True, optimizer="fused", second_stage=False, ordered_wgrad=None,
                  exchange_single_rank=False, grad_wire_dtype=None, siamese_backbone=True, supp_roialign=True,
-                 center_sample=True, loc_loss_type="giou", box_cls_loss="ce_loss"):
+                 center_sample=True, loc_loss_type="giou", box_cls_loss="ce_loss", soft_labeling=False, soft_labeling_func="linear"):
         self.center_sample, self.loc_loss_type = spec.loss_mode(center_sample, loc_loss_type)     # ValueError before anything is built
-        self.box_cls_loss = spec.box_cls_loss_mode(box_cls_loss)
+        self.soft_labeling, self.soft_labeling_func = spec.soft_labeling_mode(soft_labeling, soft_labeling_func)
+        self.box_cls_loss = spec.box_cls_loss_mode(box_cls_loss, soft_labeling=self.soft_labeling)
         if not torch.cuda.is_available():
             raise ops._lib.OsdError("TrainEngine needs an MI355X: no GPU visible and there is no CPU fallback")
         ops._lib.load()
@@ -298,7 +304,7 @@ class TrainEngine(ForwardPass, BackwardPass, SecondStage, Update, State):
         missing = [k for k in spec.box_head_shapes() if k not in sd]
         if missing:
             raise KeyError("second_stage=True needs the roi_heads.box.* entries, e.g. %s" % missing[:2])
-        spec.check_box_cls_score(sd, self.box_cls_loss, b)
+        spec.check_box_cls_score(sd, self.box_cls_loss, b, soft_labeling=self.soft_labeling)
         c, mid, p = spec.FPN_OUT, spec.FPN_OUT // 2, spec.BOX_POOL
 
         def conv(name, cout, cin, r, s, has_bias):
@@ -317,7 +323,7 @@ class TrainEngine(ForwardPass, BackwardPass, SecondStage, Update, State):
         self._plan += [(b + "feature_aggreg.1.weight", (mid,)), (b + "feature_aggreg.1.bias", (mid,))]
         conv(b + "fc6", spec.BOX_MLP_DIM, mid * p * p, 1, 1, True)
         conv(b + "fc7", spec.BOX_MLP_DIM, spec.BOX_MLP_DIM, 1, 1, True)
-        conv(b + "pred", spec.box_cls_logits(self.box_cls_loss) + 4 * spec.BOX_NUM_CLASSES, spec.BOX_MLP_DIM, 1, 1, True)
+        conv(b + "pred", spec.box_cls_logits(self.box_cls_loss, self.soft_labeling) + 4 * spec.BOX_NUM_CLASSES, spec.BOX_MLP_DIM, 1, 1, True)
 
     def _allocate(self, sd):
         total = sum(int(math.prod(s)) for _, s in self._plan)

@@ -26,8 +26,17 @@ class SecondStage(object):
         S = spec.BOX_BATCH_PER_IMAGE
         if keys is None:
             keys = torch.rand((n, P), device=self.device, dtype=torch.float32)
-        sb, sl, st, si, sc = ops.box_match_sample(pb, pc, gt_boxes, gt_count, keys, S, spec.BOX_POSITIVE_FRACTION,
-                                                  spec.BOX_FG_IOU_THRESH, spec.BOX_REG_WEIGHTS)
+        # FEW_SHOT.SOFT_LABELING: the soft labels travel from the sampler to the loss (loss.py:260-287,333-334) when the loss reads
+        # them; 'ce_loss' / 'focal_loss' never do, and make the launches they make without the option
+        soft = spec.box_loss_reads_soft_labels(self.box_cls_loss, getattr(self, "soft_labeling", False))
+        ss = None
+        if soft:
+            sb, sl, st, si, sc, ss = ops.box_match_sample(pb, pc, gt_boxes, gt_count, keys, S, spec.BOX_POSITIVE_FRACTION,
+                                                          spec.BOX_FG_IOU_THRESH, spec.BOX_REG_WEIGHTS,
+                                                          soft_func=self.soft_labeling_func)
+        else:
+            sb, sl, st, si, sc = ops.box_match_sample(pb, pc, gt_boxes, gt_count, keys, S, spec.BOX_POSITIVE_FRACTION,
+                                                      spec.BOX_FG_IOU_THRESH, spec.BOX_REG_WEIGHTS)
         M = n * S
         slope, gr, eps = spec.BOX_LEAKY_SLOPE, spec.GN_GROUPS, spec.GN_EPS
         (g0, dg0), (b0, db0) = self.extra[b + "compress_dim_conv.1.weight"], self.extra[b + "compress_dim_conv.1.bias"]
@@ -54,7 +63,7 @@ class SecondStage(object):
         f7 = ops.conv2d(f6, fc7.pc, act=ACT_RELU)
         pred = ops.conv2d(f7, cp.pc)
         losses, d_pred = ops.box_loss(pred, sl, st, sc, n, S, spec.BOX_LOSS_WEIGHTS[0], spec.BOX_LOSS_WEIGHTS[1],
-                                      grad_stride=cp.pd.cin_k, cls_loss=self.box_cls_loss)
+                                      grad_stride=cp.pd.cin_k, cls_loss=self.box_cls_loss, soft=ss)
         # ---- backward (inline on this stream: M = 1024 ROIs)
 
         def wg(c, xin, dy, pad=0):
@@ -96,7 +105,7 @@ class SecondStage(object):
                                            spec.BOX_POOL, spec.POOLER_SAMPLING_RATIO)
             gqs = list(enumerate(maps))
         self._keep.append((sb, sl, st, si, sc, q, qh, x, u0, t0, u1, t1, u2, t2, f6, f7, pred, d_pred, d_f7, d_f6, d_t2, d_u2,
-                           d_t1, d_u1, d_t0, d_u0, d_x, d_qh, d_q, keys))
+                           d_t1, d_u1, d_t0, d_u0, d_x, d_qh, d_q, keys, ss))
         if want_debug:
-            self.last_box = dict(boxes=sb, labels=sl, targets=st, index=si, counts=sc, pred=pred)
+            self.last_box = dict(boxes=sb, labels=sl, targets=st, index=si, counts=sc, pred=pred, soft=ss)
         return losses, gx, gqs
