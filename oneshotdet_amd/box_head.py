@@ -54,7 +54,7 @@ def check_shots(box_cls_loss, shots):
     """Inference with several queries per image exists for 'ce_loss' only: in the one-logit modes the reference's arg-max over
     shots builds a 4-column index ([M, 1] logits) for the 8 regression columns and raises IndexError (box_head.py:246-253).
     Training is unaffected: it uses the first query only (box_head.py:123-203)."""
-    if shots > 1 and box_cls_loss not in ("ce_loss", "cxe_loss"):          # 'cxe_loss' has two logits: it scores and decodes as 'ce_loss'
+    if shots > 1 and spec.BOX_CLS_MODES[box_cls_loss].logits != 2:         # 'cxe_loss' has two logits: it scores and decodes as 'ce_loss'
         raise ValueError("box_cls_loss=%r with %d shots: the reference's arg-max over shots indexes the 8 regression columns of a "
                          "one-logit predictor with a 4-column index and raises IndexError (box_head.py:246-253); the second stage "
                          "detects with one shot in this mode" % (box_cls_loss, shots))

@@ -460,23 +460,16 @@ extern "C" int osd_box_decode_opt(const void* pred, const float* rois, const int
     return osd_fail(OSD_ERR_INVALID_ARG, "box_decode: bad args");
   if (n * max_rois == 0) return OSD_OK;
   const float clip = 4.135166556742356f;   // log(1000/16), box_coder.py:19
-  const int g = grid_for((long long)n * max_rois, 256);
-  if (dtype == OSD_F32 && ce)
-    hipLaunchKernelGGL(box_decode_kernel<float>, dim3(g), dim3(256), 0, OSD_STREAM(stream), (const float*)pred, rois, counts,
-                       scores, boxes, logits_out, reg_out, n, max_rois, shots, pred_stride, reg_weights[0], reg_weights[1],
-                       reg_weights[2], reg_weights[3], clip, img_h, img_w, score_thresh, img_hw);
-  else if (dtype == OSD_BF16 && ce)
-    hipLaunchKernelGGL(box_decode_kernel<__bf16>, dim3(g), dim3(256), 0, OSD_STREAM(stream), (const __bf16*)pred, rois, counts,
-                       scores, boxes, logits_out, reg_out, n, max_rois, shots, pred_stride, reg_weights[0], reg_weights[1],
-                       reg_weights[2], reg_weights[3], clip, img_h, img_w, score_thresh, img_hw);
-  else if (dtype == OSD_F32)
-    hipLaunchKernelGGL(box_decode_sigmoid_kernel<float>, dim3(g), dim3(256), 0, OSD_STREAM(stream), (const float*)pred, rois, counts,
-                       scores, boxes, logits_out, reg_out, n, max_rois, shots, pred_stride, reg_weights[0], reg_weights[1],
-                       reg_weights[2], reg_weights[3], clip, img_h, img_w, score_thresh, img_hw);
+  // the softmax kernel and the sigmoid kernel share their argument list: one launch, templated on the kernel and its element type
+  auto launch = [&](auto kernel, auto* p) {
+    hipLaunchKernelGGL(kernel, dim3(grid_for((long long)n * max_rois, 256)), dim3(256), 0, OSD_STREAM(stream), p, rois, counts, scores,
+                       boxes, logits_out, reg_out, n, max_rois, shots, pred_stride, reg_weights[0], reg_weights[1], reg_weights[2],
+                       reg_weights[3], clip, img_h, img_w, score_thresh, img_hw);
+  };
+  if (dtype == OSD_F32)
+    launch(ce ? box_decode_kernel<float> : box_decode_sigmoid_kernel<float>, (const float*)pred);
   else if (dtype == OSD_BF16)
-    hipLaunchKernelGGL(box_decode_sigmoid_kernel<__bf16>, dim3(g), dim3(256), 0, OSD_STREAM(stream), (const __bf16*)pred, rois,
-                       counts, scores, boxes, logits_out, reg_out, n, max_rois, shots, pred_stride, reg_weights[0], reg_weights[1],
-                       reg_weights[2], reg_weights[3], clip, img_h, img_w, score_thresh, img_hw);
+    launch(ce ? box_decode_kernel<__bf16> : box_decode_sigmoid_kernel<__bf16>, (const __bf16*)pred);
   else
     return osd_fail(OSD_ERR_INVALID_ARG, "bad dtype %d", dtype);
   return osd_check_launch("box_decode");

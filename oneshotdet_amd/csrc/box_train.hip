@@ -762,23 +762,41 @@ __global__ __launch_bounds__(256) void roi_pool_levels_bwd_kernel(PoolGradLevels
 }  // namespace
 
 #define OSD_STREAM(s) reinterpret_cast<hipStream_t>(s)
+#include <type_traits>
+
+// osd_box_match_sample (s_soft null) and osd_box_match_sample_soft (which has checked soft_func and s_soft); `who` names the entry
+static int box_match_sample_launch(const char* who, const float* boxes, const int32_t* counts, const float* gt_boxes,
+                                   const int32_t* gt_count, const int32_t* gt_labels, const float* keys, int n, int max_props,
+                                   int max_gt, int batch_per_image, float positive_fraction, float iou_thresh,
+                                   const float* reg_weights, float* s_boxes, int32_t* s_labels, float* s_targets, int32_t* s_index,
+                                   int32_t* s_count, int32_t* all_labels, int32_t* all_matched, int soft_func, float* s_soft,
+                                   float* all_soft, void* stream) {
+  if (!boxes || !gt_boxes || !gt_count || !keys || !reg_weights || !s_boxes || !s_labels || !s_targets || !s_index || !s_count)
+    return osd_fail(OSD_ERR_INVALID_ARG, "%s: null argument", who);
+  if (n == 0) return OSD_OK;
+  if (max_props <= 0 || max_props > kMaxProps) return osd_fail(OSD_ERR_UNSUPPORTED, "%s: 1..%d proposals per image", who, kMaxProps);
+  if (max_gt <= 0 || batch_per_image <= 0 || batch_per_image > max_props) return osd_fail(OSD_ERR_INVALID_ARG, "%s: bad sizes", who);
+  const int num_pos = (int)(batch_per_image * positive_fraction);      // int(self.batch_size_per_image * self.positive_fraction)
+  if (s_soft)
+    hipLaunchKernelGGL(box_match_sample_soft_kernel, dim3(n), dim3(1024), 0, OSD_STREAM(stream), boxes, counts, gt_boxes, gt_count,
+                       gt_labels, keys, max_props, max_gt, batch_per_image, num_pos, iou_thresh, reg_weights[0], reg_weights[1],
+                       reg_weights[2], reg_weights[3], s_boxes, s_labels, s_targets, s_index, s_count, all_labels, all_matched,
+                       soft_func, s_soft, all_soft);
+  else
+    hipLaunchKernelGGL(box_match_sample_kernel, dim3(n), dim3(1024), 0, OSD_STREAM(stream), boxes, counts, gt_boxes, gt_count,
+                       gt_labels, keys, max_props, max_gt, batch_per_image, num_pos, iou_thresh, reg_weights[0], reg_weights[1],
+                       reg_weights[2], reg_weights[3], s_boxes, s_labels, s_targets, s_index, s_count, all_labels, all_matched);
+  return osd_check_launch(who);
+}
 
 extern "C" int osd_box_match_sample(const float* boxes, const int32_t* counts, const float* gt_boxes, const int32_t* gt_count,
                                     const int32_t* gt_labels, const float* keys, int n, int max_props, int max_gt,
                                     int batch_per_image, float positive_fraction, float iou_thresh, const float* reg_weights,
                                     float* s_boxes, int32_t* s_labels, float* s_targets, int32_t* s_index, int32_t* s_count,
                                     int32_t* all_labels, int32_t* all_matched, void* stream) {
-  if (!boxes || !gt_boxes || !gt_count || !keys || !reg_weights || !s_boxes || !s_labels || !s_targets || !s_index || !s_count)
-    return osd_fail(OSD_ERR_INVALID_ARG, "box_match_sample: null argument");
-  if (n == 0) return OSD_OK;
-  if (max_props <= 0 || max_props > kMaxProps) return osd_fail(OSD_ERR_UNSUPPORTED, "box_match_sample: 1..%d proposals per image", kMaxProps);
-  if (max_gt <= 0 || batch_per_image <= 0 || batch_per_image > max_props)
-    return osd_fail(OSD_ERR_INVALID_ARG, "box_match_sample: bad sizes");
-  const int num_pos = (int)(batch_per_image * positive_fraction);      // int(self.batch_size_per_image * self.positive_fraction)
-  hipLaunchKernelGGL(box_match_sample_kernel, dim3(n), dim3(1024), 0, OSD_STREAM(stream), boxes, counts, gt_boxes, gt_count,
-                     gt_labels, keys, max_props, max_gt, batch_per_image, num_pos, iou_thresh, reg_weights[0], reg_weights[1],
-                     reg_weights[2], reg_weights[3], s_boxes, s_labels, s_targets, s_index, s_count, all_labels, all_matched);
-  return osd_check_launch("box_match_sample");
+  return box_match_sample_launch("box_match_sample", boxes, counts, gt_boxes, gt_count, gt_labels, keys, n, max_props, max_gt,
+                                 batch_per_image, positive_fraction, iou_thresh, reg_weights, s_boxes, s_labels, s_targets, s_index,
+                                 s_count, all_labels, all_matched, 0, nullptr, nullptr, stream);
 }
 
 extern "C" int osd_box_match_sample_soft(const float* boxes, const int32_t* counts, const float* gt_boxes, const int32_t* gt_count,
@@ -787,39 +805,57 @@ extern "C" int osd_box_match_sample_soft(const float* boxes, const int32_t* coun
                                          float* s_boxes, int32_t* s_labels, float* s_targets, int32_t* s_index, int32_t* s_count,
                                          int32_t* all_labels, int32_t* all_matched, int soft_func, float* s_soft, float* all_soft,
                                          void* stream) {
-  if (!boxes || !gt_boxes || !gt_count || !keys || !reg_weights || !s_boxes || !s_labels || !s_targets || !s_index || !s_count ||
-      !s_soft)
-    return osd_fail(OSD_ERR_INVALID_ARG, "box_match_sample_soft: null argument");
+  if (!s_soft) return osd_fail(OSD_ERR_INVALID_ARG, "box_match_sample_soft: null argument");
   if (soft_func < OSD_SOFT_LABEL_DISCRETE || soft_func > OSD_SOFT_LABEL_TRANS_4TH_LINEAR)
     return osd_fail(OSD_ERR_INVALID_ARG, "box_match_sample_soft: soft_func %d (OSD_SOFT_LABEL_*: 0..3)", soft_func);
-  if (n == 0) return OSD_OK;
-  if (max_props <= 0 || max_props > kMaxProps)
-    return osd_fail(OSD_ERR_UNSUPPORTED, "box_match_sample_soft: 1..%d proposals per image", kMaxProps);
-  if (max_gt <= 0 || batch_per_image <= 0 || batch_per_image > max_props)
-    return osd_fail(OSD_ERR_INVALID_ARG, "box_match_sample_soft: bad sizes");
-  const int num_pos = (int)(batch_per_image * positive_fraction);
-  hipLaunchKernelGGL(box_match_sample_soft_kernel, dim3(n), dim3(1024), 0, OSD_STREAM(stream), boxes, counts, gt_boxes, gt_count,
-                     gt_labels, keys, max_props, max_gt, batch_per_image, num_pos, iou_thresh, reg_weights[0], reg_weights[1],
-                     reg_weights[2], reg_weights[3], s_boxes, s_labels, s_targets, s_index, s_count, all_labels, all_matched,
-                     soft_func, s_soft, all_soft);
-  return osd_check_launch("box_match_sample_soft");
+  return box_match_sample_launch("box_match_sample_soft", boxes, counts, gt_boxes, gt_count, gt_labels, keys, n, max_props, max_gt,
+                                 batch_per_image, positive_fraction, iou_thresh, reg_weights, s_boxes, s_labels, s_targets, s_index,
+                                 s_count, all_labels, all_matched, soft_func, s_soft, all_soft, stream);
 }
 
-template <typename T>
-static void launch_box_loss_soft(const void* pred, const int32_t* labels, const float* targets, const int32_t* s_count,
-                                 const float* soft, int n, int S, int pstride, float w_cls, float w_box, float* losses, void* d_pred,
-                                 int gstride, int cls_loss, hipStream_t st) {
-  const T* p = (const T*)pred;
-  T* d = (T*)d_pred;
-  if (cls_loss == OSD_BOX_CLS_MSE)
-    hipLaunchKernelGGL((box_loss_soft_kernel<T, kBoxClsSoftMse>), dim3(1), dim3(1024), 0, st, p, labels, targets, s_count, soft, n, S,
-                       pstride, w_cls, w_box, losses, d, gstride);
-  else if (cls_loss == OSD_BOX_CLS_L1)
-    hipLaunchKernelGGL((box_loss_soft_kernel<T, OSD_BOX_CLS_L1>), dim3(1), dim3(1024), 0, st, p, labels, targets, s_count, soft, n, S,
-                       pstride, w_cls, w_box, losses, d, gstride);
+// The three loss entries; `who` names the entry.  Each has refused the modes that are not its own: with `soft` cls_loss is
+// OSD_BOX_CLS_MSE / _L1 / _CXE, without it _CE / _FOCAL / _MSE.
+static int box_loss_launch(const char* who, const void* pred, const int32_t* labels, const float* targets, const int32_t* s_count,
+                           int n, int S, int pred_stride, float w_cls, float w_box, float* losses, void* d_pred, int grad_stride,
+                           int dtype, const float* soft, int cls_loss, float gamma, float alpha, void* stream) {
+  if (!pred || !labels || !targets || !s_count || !losses) return osd_fail(OSD_ERR_INVALID_ARG, "%s: null argument", who);
+  const int width = (cls_loss == OSD_BOX_CLS_CE || cls_loss == OSD_BOX_CLS_CXE ? 2 : 1) + 8;
+  if (pred_stride < width || (d_pred && grad_stride < width))
+    return osd_fail(OSD_ERR_INVALID_ARG, "%s: %d logits + 8 deltas per row", who, width - 8);
+  auto dispatch = [&](auto* d) {      // d_pred in the element type T; T x mode -> the kernel (three argument lists)
+    using T = std::remove_pointer_t<decltype(d)>;
+    const T* p = (const T*)pred;
+    const dim3 grid(1), block(1024);
+    hipStream_t st = OSD_STREAM(stream);
+    auto soft_launch = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, grid, block, 0, st, p, labels, targets, s_count, soft, n, S, pred_stride, w_cls, w_box, losses, d,
+                         grad_stride);
+    };
+    auto mode_launch = [&](auto kernel) {
+      hipLaunchKernelGGL(kernel, grid, block, 0, st, p, labels, targets, s_count, n, S, pred_stride, w_cls, w_box, gamma, alpha, losses,
+                         d, grad_stride);
+    };
+    if (soft && cls_loss == OSD_BOX_CLS_MSE)
+      soft_launch(box_loss_soft_kernel<T, kBoxClsSoftMse>);
+    else if (cls_loss == OSD_BOX_CLS_L1)
+      soft_launch(box_loss_soft_kernel<T, OSD_BOX_CLS_L1>);
+    else if (cls_loss == OSD_BOX_CLS_CXE)
+      soft_launch(box_loss_soft_kernel<T, OSD_BOX_CLS_CXE>);
+    else if (cls_loss == OSD_BOX_CLS_CE)
+      hipLaunchKernelGGL(box_loss_kernel<T>, grid, block, 0, st, p, labels, targets, s_count, n, S, pred_stride, w_cls, w_box, losses, d,
+                         grad_stride);
+    else if (cls_loss == OSD_BOX_CLS_FOCAL)
+      mode_launch(box_loss_mode_kernel<T, OSD_BOX_CLS_FOCAL>);
+    else
+      mode_launch(box_loss_mode_kernel<T, OSD_BOX_CLS_MSE>);
+  };
+  if (dtype == OSD_F32)
+    dispatch((float*)d_pred);
+  else if (dtype == OSD_BF16)
+    dispatch((__bf16*)d_pred);
   else
-    hipLaunchKernelGGL((box_loss_soft_kernel<T, OSD_BOX_CLS_CXE>), dim3(1), dim3(1024), 0, st, p, labels, targets, s_count, soft, n, S,
-                       pstride, w_cls, w_box, losses, d, gstride);
+    return osd_fail(OSD_ERR_INVALID_ARG, "%s: bad dtype", who);
+  return osd_check_launch(who);
 }
 
 extern "C" int osd_box_loss_soft(const void* pred, const int32_t* labels, const float* targets, const int32_t* s_count, int n,
@@ -827,64 +863,25 @@ extern "C" int osd_box_loss_soft(const void* pred, const int32_t* labels, const 
                                  int grad_stride, int dtype, const float* soft, int cls_loss, void* stream) {
   if (cls_loss != OSD_BOX_CLS_MSE && cls_loss != OSD_BOX_CLS_L1 && cls_loss != OSD_BOX_CLS_CXE)
     return osd_fail(OSD_ERR_INVALID_ARG, "box_loss_soft: cls_loss %d (OSD_BOX_CLS_MSE / _L1 / _CXE read soft labels)", cls_loss);
-  if (!pred || !labels || !targets || !s_count || !losses || !soft)
-    return osd_fail(OSD_ERR_INVALID_ARG, "box_loss_soft: null argument");
-  const int width = (cls_loss == OSD_BOX_CLS_CXE ? 2 : 1) + 8;
-  if (pred_stride < width || (d_pred && grad_stride < width))
-    return osd_fail(OSD_ERR_INVALID_ARG, "box_loss_soft: %d logits + 8 deltas per row", width - 8);
-  if (dtype == OSD_F32)
-    launch_box_loss_soft<float>(pred, labels, targets, s_count, soft, n, rois_per_image, pred_stride, w_cls, w_box, losses, d_pred,
-                                grad_stride, cls_loss, OSD_STREAM(stream));
-  else if (dtype == OSD_BF16)
-    launch_box_loss_soft<__bf16>(pred, labels, targets, s_count, soft, n, rois_per_image, pred_stride, w_cls, w_box, losses, d_pred,
-                                 grad_stride, cls_loss, OSD_STREAM(stream));
-  else
-    return osd_fail(OSD_ERR_INVALID_ARG, "box_loss_soft: bad dtype");
-  return osd_check_launch("box_loss_soft");
-}
-
-template <typename T>
-static void launch_box_loss(const void* pred, const int32_t* labels, const float* targets, const int32_t* s_count, int n, int S,
-                            int pstride, float w_cls, float w_box, float* losses, void* d_pred, int gstride, int cls_loss,
-                            float gamma, float alpha, hipStream_t st) {
-  const T* p = (const T*)pred;
-  T* d = (T*)d_pred;
-  if (cls_loss == OSD_BOX_CLS_CE)
-    hipLaunchKernelGGL(box_loss_kernel<T>, dim3(1), dim3(1024), 0, st, p, labels, targets, s_count, n, S, pstride, w_cls, w_box,
-                       losses, d, gstride);
-  else if (cls_loss == OSD_BOX_CLS_FOCAL)
-    hipLaunchKernelGGL((box_loss_mode_kernel<T, OSD_BOX_CLS_FOCAL>), dim3(1), dim3(1024), 0, st, p, labels, targets, s_count, n, S,
-                       pstride, w_cls, w_box, gamma, alpha, losses, d, gstride);
-  else
-    hipLaunchKernelGGL((box_loss_mode_kernel<T, OSD_BOX_CLS_MSE>), dim3(1), dim3(1024), 0, st, p, labels, targets, s_count, n, S,
-                       pstride, w_cls, w_box, gamma, alpha, losses, d, gstride);
+  if (!soft) return osd_fail(OSD_ERR_INVALID_ARG, "box_loss_soft: null argument");
+  return box_loss_launch("box_loss_soft", pred, labels, targets, s_count, n, rois_per_image, pred_stride, w_cls, w_box, losses, d_pred,
+                         grad_stride, dtype, soft, cls_loss, 0.f, 0.f, stream);
 }
 
 extern "C" int osd_box_loss_opt(const void* pred, const int32_t* labels, const float* targets, const int32_t* s_count, int n,
                                 int rois_per_image, int pred_stride, float w_cls, float w_box, float* losses, void* d_pred,
                                 int grad_stride, int dtype, int cls_loss, float gamma, float alpha, void* stream) {
-  if (!pred || !labels || !targets || !s_count || !losses) return osd_fail(OSD_ERR_INVALID_ARG, "box_loss: null argument");
   if (cls_loss != OSD_BOX_CLS_CE && cls_loss != OSD_BOX_CLS_FOCAL && cls_loss != OSD_BOX_CLS_MSE)
     return osd_fail(OSD_ERR_INVALID_ARG, "box_loss: cls_loss %d (OSD_BOX_CLS_CE / _FOCAL / _MSE)", cls_loss);
-  const int width = (cls_loss == OSD_BOX_CLS_CE ? 2 : 1) + 8;
-  if (pred_stride < width || (d_pred && grad_stride < width))
-    return osd_fail(OSD_ERR_INVALID_ARG, "box_loss: %d logits + 8 deltas per row", width - 8);
-  if (dtype == OSD_F32)
-    launch_box_loss<float>(pred, labels, targets, s_count, n, rois_per_image, pred_stride, w_cls, w_box, losses, d_pred, grad_stride,
-                           cls_loss, gamma, alpha, OSD_STREAM(stream));
-  else if (dtype == OSD_BF16)
-    launch_box_loss<__bf16>(pred, labels, targets, s_count, n, rois_per_image, pred_stride, w_cls, w_box, losses, d_pred, grad_stride,
-                            cls_loss, gamma, alpha, OSD_STREAM(stream));
-  else
-    return osd_fail(OSD_ERR_INVALID_ARG, "box_loss: bad dtype");
-  return osd_check_launch("box_loss");
+  return box_loss_launch("box_loss", pred, labels, targets, s_count, n, rois_per_image, pred_stride, w_cls, w_box, losses, d_pred,
+                         grad_stride, dtype, nullptr, cls_loss, gamma, alpha, stream);
 }
 
 extern "C" int osd_box_loss(const void* pred, const int32_t* labels, const float* targets, const int32_t* s_count, int n,
                             int rois_per_image, int pred_stride, float w_cls, float w_box, float* losses, void* d_pred,
                             int grad_stride, int dtype, void* stream) {
-  return osd_box_loss_opt(pred, labels, targets, s_count, n, rois_per_image, pred_stride, w_cls, w_box, losses, d_pred, grad_stride,
-                          dtype, OSD_BOX_CLS_CE, 0.f, 0.f, stream);
+  return box_loss_launch("box_loss", pred, labels, targets, s_count, n, rois_per_image, pred_stride, w_cls, w_box, losses, d_pred,
+                         grad_stride, dtype, nullptr, OSD_BOX_CLS_CE, 0.f, 0.f, stream);
 }
 
 extern "C" int osd_groupnorm_act_rois_bwd(const void* x, const void* addend, const float* gamma, const float* beta,

@@ -1307,8 +1307,7 @@ def box_decode(pred, rois, counts, reg_weights, img_h, img_w, score_thresh, want
     """pred [S, N*R, P] (L logits, then 8 deltas; L = 2 for cls_loss 'ce_loss', 1 for 'focal_loss' / 'mse_loss' whose score is
     sigmoid(logit)), rois [N,R,4] -> scores [N,R] (-1 = dropped), boxes [N,R,4] (+ the selected logits [N*R,L] and deltas [N*R,8]
     in fp32 when want_raw).  With soft_labeling, 'cxe_loss' decodes as 'ce_loss' and 'l1_loss' as 'mse_loss' (inference.py:61-69)."""
-    cls_loss = spec.box_cls_decode_mode(cls_loss, soft_labeling)
-    mode = spec.BOX_CLS_LOSSES.index(cls_loss)
+    mode = spec.BOX_CLS_MODES[spec.box_cls_decode_mode(cls_loss, soft_labeling)]
     _chk_dev(pred, rois, counts)
     s, m, p = pred.shape
     n, r, _ = rois.shape
@@ -1316,15 +1315,12 @@ def box_decode(pred, rois, counts, reg_weights, img_h, img_w, score_thresh, want
     dev = pred.device
     scores = torch.empty((n, r), device=dev, dtype=torch.float32)
     boxes = torch.empty((n, r, 4), device=dev, dtype=torch.float32)
-    lo = torch.empty((m, spec.box_cls_logits(cls_loss)), device=dev, dtype=torch.float32) if want_raw else None
+    lo = torch.empty((m, mode.logits), device=dev, dtype=torch.float32) if want_raw else None
     ro = torch.empty((m, 8), device=dev, dtype=torch.float32) if want_raw else None
     rw = (C.c_float * 4)(*[float(v) for v in reg_weights])
-    if mode == 0:
-        _lib.call("osd_box_decode", _p(pred), _ptr(rois.contiguous()), _p(counts), _p(scores), _p(boxes), _p(lo),
-                  _p(ro), n, r, s, p, rw, float(img_h), float(img_w), _p(img_hw), float(score_thresh), _dt(pred), _stream())
-    else:
-        _lib.call("osd_box_decode_opt", _p(pred), _ptr(rois.contiguous()), _p(counts), _p(scores), _p(boxes), _p(lo),
-                  _p(ro), n, r, s, p, rw, float(img_h), float(img_w), _p(img_hw), float(score_thresh), _dt(pred), mode, _stream())
+    entry, tail = ("osd_box_decode", ()) if mode.code == _lib.BOX_CLS_CE else ("osd_box_decode_opt", (mode.code,))
+    _lib.call(entry, _p(pred), _ptr(rois.contiguous()), _p(counts), _p(scores), _p(boxes), _p(lo), _p(ro), n, r, s, p, rw,
+              float(img_h), float(img_w), _p(img_hw), float(score_thresh), _dt(pred), *tail, _stream())
     return (scores, boxes, lo, ro) if want_raw else (scores, boxes)
 
 
@@ -1349,18 +1345,17 @@ def box_match_sample(boxes, counts, gt_boxes, gt_count, keys, batch_per_image, p
     am = torch.empty((n, p), device=dev, dtype=torch.int32) if want_all else None
     rw = (C.c_float * 4)(*[float(v) for v in reg_weights])
     assert keys.shape == (n, p) and keys.dtype == torch.float32
-    if func is not None:
-        ss = torch.empty((n, s), device=dev, dtype=torch.float32)
-        as_ = torch.empty((n, p), device=dev, dtype=torch.float32) if want_all else None
-        _lib.call("osd_box_match_sample_soft", _ptr(boxes.contiguous()), _p(counts), _ptr(gt_boxes.contiguous().float()), _p(gt_count),
-                  _p(gt_labels), _ptr(keys.contiguous()), n, p, gt_boxes.shape[1], s, float(positive_fraction), float(iou_thresh),
-                  rw, _p(sb), _p(sl), _p(st), _p(si), _p(sc), _p(al), _p(am), func, _p(ss), _p(as_), _stream())
-        _rec("box_match_sample_soft", boxes=boxes, soft_func=soft_func, soft=ss)       # the soft launches only: the default step's trace is unchanged
-        return (sb, sl, st, si, sc, al, am, ss, as_) if want_all else (sb, sl, st, si, sc, ss)
-    _lib.call("osd_box_match_sample", _ptr(boxes.contiguous()), _p(counts), _ptr(gt_boxes.contiguous().float()), _p(gt_count),
-              _p(gt_labels), _ptr(keys.contiguous()), n, p, gt_boxes.shape[1], s, float(positive_fraction), float(iou_thresh),
-              rw, _p(sb), _p(sl), _p(st), _p(si), _p(sc), _p(al), _p(am), _stream())
-    return (sb, sl, st, si, sc, al, am) if want_all else (sb, sl, st, si, sc)
+    args = (_ptr(boxes.contiguous()), _p(counts), _ptr(gt_boxes.contiguous().float()), _p(gt_count), _p(gt_labels),
+            _ptr(keys.contiguous()), n, p, gt_boxes.shape[1], s, float(positive_fraction), float(iou_thresh), rw, _p(sb), _p(sl),
+            _p(st), _p(si), _p(sc), _p(al), _p(am))
+    if func is None:
+        _lib.call("osd_box_match_sample", *args, _stream())
+        return (sb, sl, st, si, sc, al, am) if want_all else (sb, sl, st, si, sc)
+    ss = torch.empty((n, s), device=dev, dtype=torch.float32)
+    as_ = torch.empty((n, p), device=dev, dtype=torch.float32) if want_all else None
+    _lib.call("osd_box_match_sample_soft", *args, func, _p(ss), _p(as_), _stream())
+    _rec("box_match_sample_soft", boxes=boxes, soft_func=soft_func, soft=ss)       # the soft launches only: the default step's trace is unchanged
+    return (sb, sl, st, si, sc, al, am, ss, as_) if want_all else (sb, sl, st, si, sc, ss)
 
 
 def box_loss(pred, labels, targets, s_count, n, rois_per_image, w_cls, w_box, grad_stride=0, cls_loss="ce_loss", gamma=None,
@@ -1373,31 +1368,25 @@ def box_loss(pred, labels, targets, s_count, n, rois_per_image, w_cls, w_box, gr
     'mse_loss' (the same broadcast against the soft labels), 'l1_loss' (L = 1, the [M, M]-broadcast mean of |sigmoid - soft|) and
     'cxe_loss' (L = 2, the soft cross-entropy averaged over 2M elements); 'ce_loss' / 'focal_loss' never read soft labels and make
     the launch they make without them."""
-    soft_mode = spec.box_cls_loss_mode(cls_loss, soft_labeling=soft is not None)
-    if soft is not None and spec.box_loss_reads_soft_labels(soft_mode, True):
-        code = {"mse_loss": _lib.BOX_CLS_MSE, "l1_loss": _lib.BOX_CLS_L1, "cxe_loss": _lib.BOX_CLS_CXE}[soft_mode]
-        m = n * rois_per_image
-        pred2 = pred.reshape(m, -1)
-        assert soft.dtype == torch.float32 and soft.numel() == m and soft.is_contiguous()
-        losses = torch.empty((3,), device=pred.device, dtype=torch.float32)
-        d = torch.empty((m, grad_stride), device=pred.device, dtype=pred.dtype) if grad_stride else None
-        _lib.call("osd_box_loss_soft", _p(pred2), _p(labels), _p(targets), _p(s_count), n, rois_per_image, pred2.shape[1],
-                  float(w_cls), float(w_box), _p(losses), _p(d), int(grad_stride), _dt(pred), _p(soft), code, _stream())
-        _rec("box_loss_soft", pred=pred2, soft=soft, cls_loss=soft_mode, losses=losses, d_pred=d)
-        return losses, d
-    mode = spec.BOX_CLS_LOSSES.index(soft_mode)
+    name = spec.box_cls_loss_mode(cls_loss, soft_labeling=soft is not None)
+    code = spec.BOX_CLS_MODES[name].code
+    reads_soft = soft is not None and spec.box_loss_reads_soft_labels(name, True)
     m = n * rois_per_image
     pred2 = pred.reshape(m, -1)
     losses = torch.empty((3,), device=pred.device, dtype=torch.float32)
     d = torch.empty((m, grad_stride), device=pred.device, dtype=pred.dtype) if grad_stride else None
-    if mode == 0:
-        _lib.call("osd_box_loss", _p(pred2), _p(labels), _p(targets), _p(s_count), n, rois_per_image, pred2.shape[1],
-                  float(w_cls), float(w_box), _p(losses), _p(d), int(grad_stride), _dt(pred), _stream())
+    if reads_soft:
+        assert soft.dtype == torch.float32 and soft.numel() == m and soft.is_contiguous()
+        entry, tail = "osd_box_loss_soft", (_p(soft), code)
+    elif code == _lib.BOX_CLS_CE:
+        entry, tail = "osd_box_loss", ()
     else:
-        _lib.call("osd_box_loss_opt", _p(pred2), _p(labels), _p(targets), _p(s_count), n, rois_per_image, pred2.shape[1],
-                  float(w_cls), float(w_box), _p(losses), _p(d), int(grad_stride), _dt(pred), mode,
-                  float(spec.LOSS_GAMMA if gamma is None else gamma), float(spec.BOX_LOSS_ALPHA if alpha is None else alpha),
-                  _stream())
+        entry, tail = "osd_box_loss_opt", (code, float(spec.LOSS_GAMMA if gamma is None else gamma),
+                                           float(spec.BOX_LOSS_ALPHA if alpha is None else alpha))
+    _lib.call(entry, _p(pred2), _p(labels), _p(targets), _p(s_count), n, rois_per_image, pred2.shape[1], float(w_cls), float(w_box),
+              _p(losses), _p(d), int(grad_stride), _dt(pred), *tail, _stream())
+    if reads_soft:
+        _rec("box_loss_soft", pred=pred2, soft=soft, cls_loss=name, losses=losses, d_pred=d)
     return losses, d
 
 

@@ -6,7 +6,7 @@ config of record configs/fcos/2019_10_25_vanilla_siamse_backbone.yaml + config/d
 tests/test_spec.py checks this list against tests/golden/state_dict_keys.json, which was dumped from the real
 reference model.
 """
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 
 # ---- config of record (only the values the hot path reads; SURVEY.md §5) ----
 STEM_OUT = 64
@@ -49,11 +49,26 @@ BOX_BATCH_PER_IMAGE = 128             # ROI_HEADS.BATCH_SIZE_PER_IMAGE
 BOX_POSITIVE_FRACTION = 0.25          # ROI_HEADS.POSITIVE_FRACTION
 BOX_LOSS_WEIGHTS = (5.0, 2.5)         # loss_classifier *= 5; loss_box_reg *= 2.5
 BOX_CLS_LOSS = "ce_loss"               # yaml / defaults.py:511 FEW_SHOT.SECOND_STAGE_CLS_LOSS
-BOX_CLS_LOSSES = ("ce_loss", "focal_loss", "mse_loss")      # index = OSD_BOX_CLS_* of include/oneshotdet_hip_box_modes.h
+# The classification-loss modes (FEW_SHOT.SECOND_STAGE_CLS_LOSS), one row each, and everything the code asks about one:
+#   code       OSD_BOX_CLS_* of include/oneshotdet_hip_box_modes.h (0..2) and include/oneshotdet_hip_soft_labels.h (3, 4)
+#   logits     outputs of predictor.cls_score (roi_box_predictors.py:47-50,63-68,76-77): 2 = softmax, 1 = sigmoid
+#   decode     the mode whose decode it uses (inference.py:61-69)
+#   soft_only  None, or the box_head/loss.py lines of a loss that exists with FEW_SHOT.SOFT_LABELING only (loss.py:364-369)
+#   reads_soft whether the loss reads the soft labels when SOFT_LABELING is on; 'ce_loss' and 'focal_loss' compute them in the
+#              reference and never read them (loss.py:343-359)
+BoxClsMode = namedtuple("BoxClsMode", "code logits decode soft_only reads_soft")
+BOX_CLS_MODES = OrderedDict((
+    ("ce_loss", BoxClsMode(0, 2, "ce_loss", None, False)),
+    ("focal_loss", BoxClsMode(1, 1, "focal_loss", None, False)),
+    ("mse_loss", BoxClsMode(2, 1, "mse_loss", None, True)),
+    ("l1_loss", BoxClsMode(3, 1, "mse_loss", "364-365", True)),
+    ("cxe_loss", BoxClsMode(4, 2, "ce_loss", "366-367", True)),
+))
+BOX_CLS_LOSSES = tuple(m for m, row in BOX_CLS_MODES.items() if not row.soft_only)       # ce, focal, mse: index = code
 SOFT_LABELING = False                  # yaml / defaults.py FEW_SHOT.SOFT_LABELING: IoU soft labels carried through the sampler (box_head/loss.py:52-62)
 SOFT_LABELING_FUNC = "linear"          # FEW_SHOT.SOFT_LABELING_FUNC (box_head/loss.py:81-104)
 SOFT_LABELING_FUNCS = ("discrete", "linear", "transLinear", "trans4thLinear")     # index = OSD_SOFT_LABEL_* of include/oneshotdet_hip_soft_labels.h
-BOX_CLS_LOSSES_SOFT = ("l1_loss", "cxe_loss")     # only with SOFT_LABELING (box_head/loss.py:364-369): OSD_BOX_CLS_L1 / OSD_BOX_CLS_CXE = 3 / 4
+BOX_CLS_LOSSES_SOFT = tuple(m for m, row in BOX_CLS_MODES.items() if row.soft_only)      # l1, cxe: only with SOFT_LABELING
 BOX_LOSS_ALPHA = 0.25                 # FEW_SHOT.SECOND_STAGE_LOSS_ALPHA (defaults.py:512); gamma is FCOS.LOSS_GAMMA (box_head/loss.py:40-44)
 LEVEL_MAP_SCALE = 224                 # poolers.py:16 LevelMapper canonical_scale / canonical_level / eps
 LEVEL_MAP_LEVEL = 4
@@ -67,10 +82,8 @@ def loss_mode(center_sample, loc_loss_type):
     return bool(center_sample), str(loc_loss_type)
 
 
-_BOX_CLS_REFUSED = {
-    "l1_loss": "it needs FEW_SHOT.SOFT_LABELING (IoU soft labels carried through the sampler, box_head/loss.py:52-64,364-365): pass soft_labeling=True",
-    "cxe_loss": "it needs FEW_SHOT.SOFT_LABELING (IoU soft labels carried through the sampler, box_head/loss.py:52-64,366-367): pass soft_labeling=True",
-}
+_BOX_CLS_REFUSED = {m: "it needs FEW_SHOT.SOFT_LABELING (IoU soft labels carried through the sampler, box_head/loss.py:52-64,%s): "
+                       "pass soft_labeling=True" % BOX_CLS_MODES[m].soft_only for m in BOX_CLS_LOSSES_SOFT}
 
 
 def soft_labeling_mode(soft_labeling=False, soft_labeling_func="linear"):
@@ -84,14 +97,13 @@ def soft_labeling_mode(soft_labeling=False, soft_labeling_func="linear"):
 def box_loss_reads_soft_labels(box_cls_loss, soft_labeling=False):
     """Whether the loss launch reads the soft labels: 'mse_loss' / 'l1_loss' / 'cxe_loss' with SOFT_LABELING.  'ce_loss' and
     'focal_loss' compute soft labels in the reference and never read them (box_head/loss.py:343-359): nothing changes for them."""
-    return bool(soft_labeling) and box_cls_loss_mode(box_cls_loss, soft_labeling=True) in ("mse_loss",) + BOX_CLS_LOSSES_SOFT
+    return bool(soft_labeling) and BOX_CLS_MODES[box_cls_loss_mode(box_cls_loss, soft_labeling=True)].reads_soft
 
 
 def box_cls_decode_mode(box_cls_loss, soft_labeling=False):
     """The BOX_CLS_LOSSES name whose decode a mode uses (inference.py:61-69): 'cxe_loss' scores like 'ce_loss' (softmax of two logits),
     'l1_loss' like 'mse_loss' (sigmoid of one)."""
-    mode = box_cls_loss_mode(box_cls_loss, soft_labeling=soft_labeling)
-    return {"l1_loss": "mse_loss", "cxe_loss": "ce_loss"}.get(mode, mode)
+    return BOX_CLS_MODES[box_cls_loss_mode(box_cls_loss, soft_labeling=soft_labeling)].decode
 
 
 def box_cls_loss_mode(box_cls_loss, loss_weighted=False, neg_support=False, method="concat", soft_labeling=False):
@@ -105,20 +117,19 @@ def box_cls_loss_mode(box_cls_loss, loss_weighted=False, neg_support=False, meth
         raise ValueError("FEW_SHOT.NEG_SUPPORT is not supported: the second stage runs without negative support")
     if method != "concat":
         raise ValueError("FEW_SHOT.SECOND_STAGE_METHOD %r is not supported: only 'concat' (not 'rn' or 'matching')" % (method,))
-    if soft_labeling and box_cls_loss in BOX_CLS_LOSSES_SOFT:
-        return str(box_cls_loss)
-    if box_cls_loss in _BOX_CLS_REFUSED:
-        raise ValueError("box_cls_loss %r is not supported: %s" % (box_cls_loss, _BOX_CLS_REFUSED[box_cls_loss]))
-    if box_cls_loss not in BOX_CLS_LOSSES:
+    row = BOX_CLS_MODES.get(box_cls_loss)
+    if row is None:
         raise ValueError("box_cls_loss must be one of %s (FEW_SHOT.SECOND_STAGE_CLS_LOSS), not %r"
                          % (", ".join(BOX_CLS_LOSSES), box_cls_loss))
+    if row.soft_only and not soft_labeling:
+        raise ValueError("box_cls_loss %r is not supported: %s" % (box_cls_loss, _BOX_CLS_REFUSED[box_cls_loss]))
     return str(box_cls_loss)
 
 
 def box_cls_logits(box_cls_loss="ce_loss", soft_labeling=False):
     """Outputs of predictor.cls_score = logits at the head of a predictor row (roi_box_predictors.py:47-50,63-68,76-77): 2 for
     'ce_loss' and 'cxe_loss', 1 for the sigmoid losses ('focal_loss', 'mse_loss', 'l1_loss')."""
-    return BOX_NUM_CLASSES if box_cls_loss_mode(box_cls_loss, soft_labeling=soft_labeling) in ("ce_loss", "cxe_loss") else 1
+    return BOX_CLS_MODES[box_cls_loss_mode(box_cls_loss, soft_labeling=soft_labeling)].logits
 
 
 def check_box_cls_score(sd, box_cls_loss, prefix="roi_heads.box.", who="the engine", soft_labeling=False):
@@ -128,7 +139,7 @@ def check_box_cls_score(sd, box_cls_loss, prefix="roi_heads.box.", who="the engi
     for leaf in ("weight", "bias"):
         rows = int(sd[prefix + "predictor.cls_score." + leaf].shape[0])
         if rows != want:
-            other = [m for m in BOX_CLS_LOSSES if box_cls_logits(m) == rows]
+            other = [m for m in BOX_CLS_LOSSES if BOX_CLS_MODES[m].logits == rows]
             raise ValueError("%spredictor.cls_score.%s has %d row(s) but box_cls_loss=%r has %d logit(s) per ROI%s"
                              % (prefix, leaf, rows, box_cls_loss, want,
                                 ": build %s with box_cls_loss=%s" % (who, " or ".join(repr(m) for m in other)) if other else ""))
