@@ -39,16 +39,20 @@ def main():
     ap.add_argument("--box-cls-loss", default=spec.BOX_CLS_LOSS, choices=list(spec.BOX_CLS_LOSSES + spec.BOX_CLS_LOSSES_SOFT),
                     help="second-stage classification loss the model was trained with (FEW_SHOT.SECOND_STAGE_CLS_LOSS): "
                          "the sigmoid losses have one class logit and a sigmoid score")
+    ap.add_argument("--linear-fusion", action="store_true",
+                    help="the model was trained with FEW_SHOT.LINEAR_FUSION: no compress_dim_conv, a 512-channel feature_aggreg.0")
     args = ap.parse_args()
     siamese = not args.shared_backbone
     roialign = not args.no_supp_roialign
     if args.checkpoint:
         siamese = checkpoint.has_query_backbone(args.checkpoint)       # the file's own mode
-    shapes = spec.hot_path_shapes(siamese) if args.first_stage_only else spec.full_model_shapes(siamese, box_cls_loss=args.box_cls_loss, soft_labeling=args.soft_labeling)
+    shapes = spec.hot_path_shapes(siamese) if args.first_stage_only else spec.full_model_shapes(
+        siamese, box_cls_loss=args.box_cls_loss, soft_labeling=args.soft_labeling, linear_fusion=args.linear_fusion)
     defaults = {k: torch.from_numpy(v) for k, v in synth.make_state_dict(shapes).items()}
     if args.checkpoint:
         sd, extras = checkpoint.load_checkpoint(args.checkpoint, defaults=defaults, siamese_backbone=siamese,
-                                                box_cls_loss=args.box_cls_loss, soft_labeling=args.soft_labeling)
+                                                box_cls_loss=args.box_cls_loss, soft_labeling=args.soft_labeling,
+                                                linear_fusion=args.linear_fusion)
         print("loaded", args.checkpoint, "(%s backbone)" % ("siamese" if siamese else "shared"),
               {k: v for k, v in extras.items() if not isinstance(v, dict)})
         if "box_cls_loss" in extras and str(extras["box_cls_loss"]) != args.box_cls_loss and not args.first_stage_only:
@@ -59,13 +63,14 @@ def main():
                 args.checkpoint, bool(extras["supp_roialign"]), "drop" if roialign is False else "add"))
     elif args.c2:
         sd = checkpoint.load_c2_resnet(args.c2, defaults, siamese_backbone=siamese, box_cls_loss=args.box_cls_loss,
-                                       soft_labeling=args.soft_labeling)
+                                       soft_labeling=args.soft_labeling, linear_fusion=args.linear_fusion)
         print("backbones initialised from", args.c2)
     else:
         sd = defaults
         print("synthetic weights (no checkpoint given)")
     det = modules.OneShotDetector(sd, dtype=torch.bfloat16 if args.dtype == "bf16" else torch.float32, siamese_backbone=siamese,
-                                  supp_roialign=roialign, box_cls_loss=args.box_cls_loss, soft_labeling=args.soft_labeling)
+                                  supp_roialign=roialign, box_cls_loss=args.box_cls_loss, soft_labeling=args.soft_labeling,
+                                  linear_fusion=args.linear_fusion and not args.first_stage_only)
     # two targets and two queries of different sizes
     targets = [torch.from_numpy(synth.make_images("ex.t%d" % i, 1, h, w)[0]) for i, (h, w) in enumerate([(480, 640), (512, 384)])]
     queries = [torch.from_numpy(synth.make_images("ex.q%d" % i, 1, h, w)[0]) for i, (h, w) in enumerate([(127, 127), (96, 160)])]

@@ -72,6 +72,8 @@ def main():
     ap.add_argument("--soft-labeling", action="store_true", help="IoU soft labels for the second stage (FEW_SHOT.SOFT_LABELING)")
     ap.add_argument("--soft-labeling-func", default=spec.SOFT_LABELING_FUNC, choices=list(spec.SOFT_LABELING_FUNCS),
                     help="soft label as a function of the IoU (FEW_SHOT.SOFT_LABELING_FUNC)")
+    ap.add_argument("--linear-fusion", action="store_true",
+                    help="box head: one 3x3 conv over cat(x, query) in front of fc6, no compress_dim_conv (FEW_SHOT.LINEAR_FUSION)")
     args = ap.parse_args()
     if not args.first_stage_only:
         spec.box_cls_loss_mode(args.box_cls_loss, soft_labeling=args.soft_labeling)      # l1_loss / cxe_loss without --soft-labeling: refused here
@@ -81,13 +83,15 @@ def main():
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
     dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float32
-    shapes = spec.hot_path_shapes(siamese) if args.first_stage_only else spec.full_model_shapes(siamese, box_cls_loss=args.box_cls_loss, soft_labeling=args.soft_labeling)
+    shapes = spec.hot_path_shapes(siamese) if args.first_stage_only else spec.full_model_shapes(
+        siamese, box_cls_loss=args.box_cls_loss, soft_labeling=args.soft_labeling, linear_fusion=args.linear_fusion)
 
     def make_engine(sd):
         return train.TrainEngine(sd, dtype=dtype, lr=0.0005, second_stage=not args.first_stage_only, siamese_backbone=siamese,
                                  supp_roialign=roialign, center_sample=center_sample, loc_loss_type=args.loc_loss_type,
                                  box_cls_loss=args.box_cls_loss, soft_labeling=args.soft_labeling,
-                                 soft_labeling_func=args.soft_labeling_func)
+                                 soft_labeling_func=args.soft_labeling_func,
+                                 linear_fusion=args.linear_fusion and not args.first_stage_only)
     start = 0
     last = os.path.join(args.out, "last_checkpoint")
     if args.resume and os.path.exists(last):
@@ -96,7 +100,8 @@ def main():
                                                 loc_loss_type=args.loc_loss_type,
                                                 box_cls_loss=None if args.first_stage_only else args.box_cls_loss,
                                                 soft_labeling=None if args.first_stage_only else args.soft_labeling,
-                                                soft_labeling_func=None if args.first_stage_only else args.soft_labeling_func)
+                                                soft_labeling_func=None if args.first_stage_only else args.soft_labeling_func,
+                                                linear_fusion=None if args.first_stage_only else args.linear_fusion)
         print("resumed at iteration", start)
     else:
         eng = make_engine(synth.make_state_dict(shapes))      # or checkpoint.load_checkpoint / load_c2_resnet, see detect.py

@@ -23,20 +23,29 @@ from .ops import ACT_NONE, ACT_RELU, PackedConv
 class BoxHeadWeights(object):
     """Packed `roi_heads.box.*` (spec.box_head_shapes)."""
 
-    def __init__(self, sd, dtype, prefix="roi_heads.box.", box_cls_loss="ce_loss", soft_labeling=False):
+    def __init__(self, sd, dtype, prefix="roi_heads.box.", box_cls_loss="ce_loss", soft_labeling=False, linear_fusion=False):
         self.soft_labeling = bool(soft_labeling)
+        self.linear_fusion = spec.check_linear_fusion(sd, linear_fusion, prefix)        # before anything is packed
         self.box_cls_loss = spec.box_cls_loss_mode(box_cls_loss, soft_labeling=self.soft_labeling)
         spec.check_box_cls_score(sd, self.box_cls_loss, prefix, soft_labeling=self.soft_labeling)      # a 1-row cls_score must never be read as two logits
         c = spec.FPN_OUT
-        w0, b0 = sd[prefix + "compress_dim_conv.0.weight"], sd[prefix + "compress_dim_conv.0.bias"]
-        self.conv0_x = ops.pack_conv(w0[:, :c].contiguous(), bias=None, dtype=dtype)          # ROI half, no bias
-        self.conv0_q = ops.pack_conv(w0[:, c:].contiguous(), bias=b0, dtype=dtype)            # query half + bias
-        self.conv3 = ops.pack_conv(sd[prefix + "compress_dim_conv.3.weight"], bias=sd[prefix + "compress_dim_conv.3.bias"],
-                                   dtype=dtype)
-        self.aggreg = ops.pack_conv(sd[prefix + "feature_aggreg.0.weight"], bias=sd[prefix + "feature_aggreg.0.bias"],
-                                    dtype=dtype)
-        self.gn = [tuple(sd[prefix + name + "." + leaf].float().contiguous() for leaf in ("weight", "bias"))
-                   for name in ("compress_dim_conv.1", "compress_dim_conv.4", "feature_aggreg.1")]
+        if self.linear_fusion:
+            # FEW_SHOT.LINEAR_FUSION: the 3x3 conv over cat(x, query), split at the concatenation like the 1x1 conv below (zero
+            # padding commutes with the split): conv3x3(cat(x, q)) = W_x * x + (W_q * q + b)
+            wa, ba = sd[prefix + "feature_aggreg.0.weight"], sd[prefix + "feature_aggreg.0.bias"]
+            self.aggreg_x = ops.pack_conv(wa[:, :c].contiguous(), bias=None, dtype=dtype)     # ROI half, no bias
+            self.aggreg_q = ops.pack_conv(wa[:, c:].contiguous(), bias=ba, dtype=dtype)       # query half + bias
+            self.gn = [tuple(sd[prefix + "feature_aggreg.1." + leaf].float().contiguous() for leaf in ("weight", "bias"))]
+        else:
+            w0, b0 = sd[prefix + "compress_dim_conv.0.weight"], sd[prefix + "compress_dim_conv.0.bias"]
+            self.conv0_x = ops.pack_conv(w0[:, :c].contiguous(), bias=None, dtype=dtype)          # ROI half, no bias
+            self.conv0_q = ops.pack_conv(w0[:, c:].contiguous(), bias=b0, dtype=dtype)            # query half + bias
+            self.conv3 = ops.pack_conv(sd[prefix + "compress_dim_conv.3.weight"], bias=sd[prefix + "compress_dim_conv.3.bias"],
+                                       dtype=dtype)
+            self.aggreg = ops.pack_conv(sd[prefix + "feature_aggreg.0.weight"], bias=sd[prefix + "feature_aggreg.0.bias"],
+                                        dtype=dtype)
+            self.gn = [tuple(sd[prefix + name + "." + leaf].float().contiguous() for leaf in ("weight", "bias"))
+                       for name in ("compress_dim_conv.1", "compress_dim_conv.4", "feature_aggreg.1")]
         p, mid = spec.BOX_POOL, c // 2
         # fc6 columns are (c, h, w) in the reference (x.view(N, -1) of NCHW, box_head.py:151); as an OIHW conv weight the
         # packer writes them in (h, w, c) order = the flattening of this build's NHWC ROI maps
@@ -91,18 +100,23 @@ def run_box_head(bw, feats, qfeats, q_size, boxes, counts, img_h, img_w, shots=1
     check_shots(bw.box_cls_loss, shots)                                                # nothing has been launched yet
     q = run_query_roi(qfeats, q_size, dtype)                                           # [N*S,7,7,C]
     assert q.shape[0] == n * shots
-    q_half = ops.conv2d(q, bw.conv0_q)                                                 # [N*S,7,7,512]  W_q q + b
+    linear = bw.linear_fusion
+    # FEW_SHOT.LINEAR_FUSION (box_head.py:61-72,148): the head in front of fc6 is the split 3x3 conv, GroupNorm, LeakyReLU
+    conv_q, conv_x, pad = (bw.aggreg_q, bw.aggreg_x, 1) if linear else (bw.conv0_q, bw.conv0_x, 0)
+    q_half = ops.conv2d(q, conv_q, pad=pad)                                            # [N*S,7,7,512 | 128]  W_q q + b
     x = ops.roi_pool_levels(feats, spec.POOLER_SCALES, boxes, counts, spec.BOX_POOL, spec.POOLER_SAMPLING_RATIO)
-    u0 = ops.conv2d(x, bw.conv0_x)                                                     # [N*R,7,7,512]  W_x x
+    u0 = ops.conv2d(x, conv_x, pad=pad)                                                # [N*R,7,7,512 | 128]  W_x x, once for all shots
     preds = torch.empty((shots, n * r, bw.pred.cout_store), device=boxes.device, dtype=dtype)
     for s in range(shots):                                                             # box_head.py:122
-        (g0, b0), (g1, b1), (g2, b2) = bw.gn
+        g0, b0 = bw.gn[0]
         t = ops.groupnorm_act_rois(u0, g0, b0, spec.GN_GROUPS, spec.GN_EPS, spec.BOX_LEAKY_SLOPE, addend=q_half,
                                    rois_per_add=r, add_stride=shots, add_offset=s)
-        t = ops.conv2d(t, bw.conv3)
-        t = ops.groupnorm_act_rois(t, g1, b1, spec.GN_GROUPS, spec.GN_EPS, spec.BOX_LEAKY_SLOPE, out=t)
-        t = ops.conv2d(t, bw.aggreg, pad=1)
-        t = ops.groupnorm_act_rois(t, g2, b2, spec.GN_GROUPS, spec.GN_EPS, spec.BOX_LEAKY_SLOPE, out=t)
+        if not linear:
+            (g1, b1), (g2, b2) = bw.gn[1:]
+            t = ops.conv2d(t, bw.conv3)
+            t = ops.groupnorm_act_rois(t, g1, b1, spec.GN_GROUPS, spec.GN_EPS, spec.BOX_LEAKY_SLOPE, out=t)
+            t = ops.conv2d(t, bw.aggreg, pad=1)
+            t = ops.groupnorm_act_rois(t, g2, b2, spec.GN_GROUPS, spec.GN_EPS, spec.BOX_LEAKY_SLOPE, out=t)
         t = ops.conv2d(t.view(n * r, 1, 1, -1), bw.fc6, act=ACT_RELU)
         t = ops.conv2d(t, bw.fc7, act=ACT_RELU)
         ops.conv2d(t, bw.pred, act=ACT_NONE, out=preds[s].view(n * r, 1, 1, -1))

@@ -19,6 +19,9 @@ training checkpoints record the mode and `resume_training` refuses to continue a
 soft_labeling / soft_labeling_func (FEW_SHOT.SOFT_LABELING / SOFT_LABELING_FUNC) change no key and no shape by themselves ('l1_loss'
 has 'mse_loss's shapes, 'cxe_loss' has 'ce_loss's): training checkpoints record both, a file without the fields was trained with
 (False, "linear"), and `resume_training` refuses a mismatch.
+linear_fusion (FEW_SHOT.LINEAR_FUSION) changes the KEY SET: with it there is no `roi_heads.box.compress_dim_conv.*` and
+`feature_aggreg.0.weight` has 512 input channels.  Loading a file trained with the other setting raises a ValueError that names the
+option (spec.check_linear_fusion) before any key is looked up; training checkpoints record it, a file without the field means False.
 """
 import os
 import pickle
@@ -78,21 +81,23 @@ def has_query_backbone(path_or_sd):
     return any(k.startswith("supp_backbone.") for k in strip_prefix_if_present(sd))
 
 
-def load_checkpoint(path, second_stage=None, defaults=None, siamese_backbone=True, box_cls_loss="ce_loss", soft_labeling=False):
+def load_checkpoint(path, second_stage=None, defaults=None, siamese_backbone=True, box_cls_loss="ce_loss", soft_labeling=False,
+                    linear_fusion=False):
     """Read a reference `.pth` (or a bare state_dict file) -> (state_dict under the reference's key names, extras).
     second_stage: True = require roi_heads.box.*, False = first stage only, None = take it when present.
     defaults: values for keys the file lacks (utils/checkpoint.py:107-115 keeps the model's own initialisation for
     FEW_SHOT.UNLOAD_KEYWORD modules); without it a missing key is an error.
     siamese_backbone=False: read the shared-backbone model's keys only (any `supp_backbone.*` in the file is ignored).
     box_cls_loss: the second stage's classification loss the file was trained with (the shape of its cls_score); 'l1_loss' /
-    'cxe_loss' with soft_labeling=True."""
+    'cxe_loss' with soft_labeling=True.  linear_fusion: FEW_SHOT.LINEAR_FUSION of the model that wrote the file."""
     data = _read(path)
     loaded = data.pop("model")
     shapes = spec.hot_path_shapes(siamese_backbone)
-    box = spec.box_head_shapes(box_cls_loss=box_cls_loss, soft_labeling=soft_labeling)
+    box = spec.box_head_shapes(box_cls_loss=box_cls_loss, soft_labeling=soft_labeling, linear_fusion=linear_fusion)
     probe = strip_prefix_if_present(loaded)
     has_box = any(k.endswith("box.fc6.weight") for k in probe)
     if second_stage or (second_stage is None and has_box):
+        _check_linear_fusion_file(probe, linear_fusion, path)
         shapes.update(box)
     sd, missing = align_state_dict(shapes, loaded)
     for k in list(missing):
@@ -102,6 +107,18 @@ def load_checkpoint(path, second_stage=None, defaults=None, siamese_backbone=Tru
     if missing:
         raise KeyError("%s lacks %d expected entries, e.g. %s" % (path, len(missing), missing[:3]))
     return OrderedDict((k, sd[k]) for k in shapes), data
+
+
+def _check_linear_fusion_file(loaded, linear_fusion, path):
+    """spec.check_linear_fusion on a file's own (suffix-matched) key names; a file without any feature_aggreg.0 is left to the
+    missing-entries error."""
+    box = {}
+    for leaf in ("feature_aggreg.0.weight", "compress_dim_conv.0.weight"):
+        hit = [k for k in loaded if ("roi_heads.box." + leaf).endswith(k) or k.endswith("box." + leaf)]
+        if hit:
+            box["roi_heads.box." + leaf] = torch.as_tensor(loaded[max(hit, key=len)])
+    if "roi_heads.box.feature_aggreg.0.weight" in box:
+        spec.check_linear_fusion(box, linear_fusion, who="the loader (%s)" % path)
 
 
 def save_checkpoint(path, state_dict, tag_last=True, **extras):
@@ -123,7 +140,8 @@ def save_training_checkpoint(path, engine, iteration, tag_last=True):
     `siamese_backbone` the engine's mode (a shared engine writes no `supp_backbone.*`); `supp_roialign` its query pooling (the
     only record of it: the pooling has no weights); `center_sample` / `loc_loss_type` the FCOS loss it trained with (likewise);
     `box_cls_loss` the second stage's classification loss (the two one-logit losses have the same shapes); `soft_labeling` /
-    `soft_labeling_func` the soft labels it was held against (no weights either)."""
+    `soft_labeling_func` the soft labels it was held against (no weights either); `linear_fusion` the box head's layout (the key set
+    shows it too)."""
     return save_checkpoint(path, engine.state_dict(), tag_last=tag_last, optimizer=engine.optimizer_state_dict(),
                            iteration=int(iteration), siamese_backbone=bool(getattr(engine, "siamese_backbone", True)),
                            supp_roialign=bool(getattr(engine, "supp_roialign", True)),
@@ -131,7 +149,8 @@ def save_training_checkpoint(path, engine, iteration, tag_last=True):
                            loc_loss_type=str(getattr(engine, "loc_loss_type", spec.LOC_LOSS_TYPE)),
                            box_cls_loss=str(getattr(engine, "box_cls_loss", spec.BOX_CLS_LOSS)),
                            soft_labeling=bool(getattr(engine, "soft_labeling", spec.SOFT_LABELING)),
-                           soft_labeling_func=str(getattr(engine, "soft_labeling_func", spec.SOFT_LABELING_FUNC)))
+                           soft_labeling_func=str(getattr(engine, "soft_labeling_func", spec.SOFT_LABELING_FUNC)),
+                           linear_fusion=bool(getattr(engine, "linear_fusion", spec.LINEAR_FUSION)))
 
 
 def _loss_name(mode):
@@ -140,7 +159,7 @@ def _loss_name(mode):
 
 
 def resume_training(path, make_engine, siamese_backbone=None, supp_roialign=None, center_sample=None, loc_loss_type=None,
-                    box_cls_loss=None, soft_labeling=None, soft_labeling_func=None):
+                    box_cls_loss=None, soft_labeling=None, soft_labeling_func=None, linear_fusion=None):
     """Load a checkpoint written by save_training_checkpoint: make_engine(state_dict) -> TrainEngine; its momentum and
     step count are restored.  Returns (engine, iteration).  The file's mode (recorded by save_training_checkpoint; for
     older files: whether it holds `supp_backbone.*`) must be the engine's: a resumed run never ties or unties weights
@@ -151,8 +170,15 @@ def resume_training(path, make_engine, siamese_backbone=None, supp_roialign=None
     (True, "giou"), the only loss there was.  And for the second stage's classification loss: box_cls_loss is the caller's
     expectation (None: whatever the file holds), a file without the field was trained with "ce_loss".  And for the soft labels:
     soft_labeling / soft_labeling_func are the caller's expectations (None: whatever the file holds), a file without the fields was
-    trained with (False, "linear"); the function only matters where soft labels are on."""
+    trained with (False, "linear"); the function only matters where soft labels are on.  And for the box head's layout:
+    linear_fusion is the caller's expectation (None: whatever the file holds), a file without the field was trained with False."""
     data = _read(path)
+    fusion = data.get("linear_fusion")
+    fusion = spec.LINEAR_FUSION if fusion is None else bool(fusion)
+    if linear_fusion is not None and bool(linear_fusion) != fusion:
+        raise ValueError("%s was trained with linear_fusion=%r (FEW_SHOT.LINEAR_FUSION); resuming it with linear_fusion=%r would "
+                         "continue another model: build the engine with linear_fusion=%r"
+                         % (path, fusion, bool(linear_fusion), fusion))
     soft = (data.get("soft_labeling"), data.get("soft_labeling_func"))
     soft = spec.soft_labeling_mode(spec.SOFT_LABELING if soft[0] is None else bool(soft[0]),
                                    spec.SOFT_LABELING_FUNC if soft[1] is None else str(soft[1]))
@@ -185,8 +211,12 @@ def resume_training(path, make_engine, siamese_backbone=None, supp_roialign=None
                          "load_checkpoint(..., siamese_backbone=%r) into a fresh run instead"
                          % (path, _MODE[mode], _MODE[bool(siamese_backbone)], "untie" if siamese_backbone else "tie",
                             bool(siamese_backbone)))
-    sd, extras = load_checkpoint(path, siamese_backbone=mode, box_cls_loss=box, soft_labeling=soft[0])
+    sd, extras = load_checkpoint(path, siamese_backbone=mode, box_cls_loss=box, soft_labeling=soft[0], linear_fusion=fusion)
     eng = make_engine(sd)
+    built_fusion = bool(getattr(eng, "linear_fusion", spec.LINEAR_FUSION))
+    if built_fusion != fusion:
+        raise ValueError("%s was trained with linear_fusion=%r (FEW_SHOT.LINEAR_FUSION) but make_engine built an engine with "
+                         "linear_fusion=%r" % (path, fusion, built_fusion))
     built_soft = (bool(getattr(eng, "soft_labeling", spec.SOFT_LABELING)), str(getattr(eng, "soft_labeling_func", spec.SOFT_LABELING_FUNC)))
     if built_soft[0] != soft[0] or (soft[0] and built_soft[1] != soft[1]):
         raise ValueError("%s was trained with soft_labeling=%r, soft_labeling_func=%r but make_engine built an engine with "
@@ -250,7 +280,8 @@ def translate_c2_resnet_name(name):
     return None if leaf is None else "layer%d.%d.%s.%s" % (stage - 1, block, conv, leaf)
 
 
-def load_c2_resnet(path, defaults, second_stage=None, siamese_backbone=True, box_cls_loss="ce_loss", soft_labeling=False):
+def load_c2_resnet(path, defaults, second_stage=None, siamese_backbone=True, box_cls_loss="ce_loss", soft_labeling=False,
+                   linear_fusion=False):
     """A Detectron ResNet `.pkl` (dict of numpy blobs, optionally under "blobs"; pickled by Python 2: latin1) -> a full
     state_dict: the ResNet bodies of BOTH backbones come from the file, every other entry (FrozenBN running statistics —
     AffineChannel has none —, FPN, FCOS head, second stage) from `defaults`, as `DetectronCheckpointer.load` leaves the
@@ -264,8 +295,11 @@ def load_c2_resnet(path, defaults, second_stage=None, siamese_backbone=True, box
         if name is not None:
             loaded[name] = torch.as_tensor(blobs[k])
     shapes = spec.hot_path_shapes(siamese_backbone)
-    if second_stage or (second_stage is None and all(k in defaults for k in spec.box_head_shapes())):
-        shapes.update(spec.box_head_shapes(box_cls_loss=box_cls_loss, soft_labeling=soft_labeling))
+    box = spec.box_head_shapes(box_cls_loss=box_cls_loss, soft_labeling=soft_labeling, linear_fusion=linear_fusion)
+    if second_stage is not False and "roi_heads.box.feature_aggreg.0.weight" in defaults:
+        spec.check_linear_fusion(defaults, linear_fusion, who="the loader (defaults)")
+    if second_stage or (second_stage is None and all(k in defaults for k in box)):
+        shapes.update(box)
     body = OrderedDict((k, v) for k, v in shapes.items() if ".body." in k and not k.endswith(("running_mean", "running_var")))
     sd, missing = align_state_dict(body, loaded)
     if missing:

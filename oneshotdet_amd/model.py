@@ -372,10 +372,14 @@ class HotPathEngine(object):
     row count is refused (ValueError naming the option).
     soft_labeling / soft_labeling_func (FEW_SHOT.SOFT_LABELING / SOFT_LABELING_FUNC): how the model was trained; admits "l1_loss"
     (one logit, scored like "mse_loss") and "cxe_loss" (two logits, scored like "ce_loss", inference.py:61-69).  Detection itself
-    reads no soft label."""
+    reads no soft label.
+    linear_fusion (FEW_SHOT.LINEAR_FUSION, box_head.py:43,61-72): the second stage's head in front of fc6 is one 3x3 conv over
+    cat(x, query), GroupNorm, LeakyReLU; the state_dict has no compress_dim_conv.* and a 512-channel feature_aggreg.0.  A state_dict
+    trained with the other setting is refused (ValueError naming the option)."""
 
     def __init__(self, state_dict, dtype=torch.float32, device="cuda", siamese_backbone=True, supp_roialign=True,
-                 box_cls_loss="ce_loss", soft_labeling=False, soft_labeling_func="linear"):
+                 box_cls_loss="ce_loss", soft_labeling=False, soft_labeling_func="linear", linear_fusion=False):
+        self.linear_fusion = bool(linear_fusion)
         self.soft_labeling, self.soft_labeling_func = spec.soft_labeling_mode(soft_labeling, soft_labeling_func)
         self.box_cls_loss = spec.box_cls_loss_mode(box_cls_loss, soft_labeling=self.soft_labeling)    # ValueError before anything is built
         if not torch.cuda.is_available():
@@ -399,9 +403,12 @@ class HotPathEngine(object):
         self.head = HeadWeights(self.sd, self.dtype)
         # second stage: packed when the state_dict carries the reference's roi_heads.box.* entries
         self.box_head = None
-        if all(k in self.sd for k in spec.box_head_shapes()):
+        if "roi_heads.box.feature_aggreg.0.weight" in self.sd:
+            spec.check_linear_fusion(self.sd, self.linear_fusion)      # the other setting's file: refused by name, not passed over
+        if all(k in self.sd for k in spec.box_head_shapes(linear_fusion=self.linear_fusion)):
             from .box_head import BoxHeadWeights
-            self.box_head = BoxHeadWeights(self.sd, self.dtype, box_cls_loss=self.box_cls_loss, soft_labeling=self.soft_labeling)
+            self.box_head = BoxHeadWeights(self.sd, self.dtype, box_cls_loss=self.box_cls_loss, soft_labeling=self.soft_labeling,
+                                           linear_fusion=self.linear_fusion)
 
     def tune(self, images, queries, second_stage=False):
         """Pick, by measurement on this device, the conv algorithm (kernel generation, ring depth, tile) for every

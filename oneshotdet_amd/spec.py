@@ -69,6 +69,7 @@ SOFT_LABELING = False                  # yaml / defaults.py FEW_SHOT.SOFT_LABELI
 SOFT_LABELING_FUNC = "linear"          # FEW_SHOT.SOFT_LABELING_FUNC (box_head/loss.py:81-104)
 SOFT_LABELING_FUNCS = ("discrete", "linear", "transLinear", "trans4thLinear")     # index = OSD_SOFT_LABEL_* of include/oneshotdet_hip_soft_labels.h
 BOX_CLS_LOSSES_SOFT = tuple(m for m, row in BOX_CLS_MODES.items() if row.soft_only)      # l1, cxe: only with SOFT_LABELING
+LINEAR_FUSION = False                  # defaults.py FEW_SHOT.LINEAR_FUSION: one 3x3 conv over cat(x, query) in front of fc6 (box_head.py:43,61-72,148)
 BOX_LOSS_ALPHA = 0.25                 # FEW_SHOT.SECOND_STAGE_LOSS_ALPHA (defaults.py:512); gamma is FCOS.LOSS_GAMMA (box_head/loss.py:40-44)
 LEVEL_MAP_SCALE = 224                 # poolers.py:16 LevelMapper canonical_scale / canonical_level / eps
 LEVEL_MAP_LEVEL = 4
@@ -148,6 +149,32 @@ def check_box_cls_score(sd, box_cls_loss, prefix="roi_heads.box.", who="the engi
         raise ValueError("%spredictor.bbox_pred.weight has %d rows, expected %d" % (prefix, rows, 4 * BOX_NUM_CLASSES))
 
 
+def check_linear_fusion(sd, linear_fusion=False, prefix="roi_heads.box.", who="the engine"):
+    """The state_dict must have been trained with this FEW_SHOT.LINEAR_FUSION: with it there is no compress_dim_conv and
+    feature_aggreg.0 reads the 2 * FPN_OUT channels of cat(x, query); without it feature_aggreg.0 reads compress_dim_conv's FPN_OUT
+    (box_head.py:43-72).  ValueError that names the option and the value to pass, before anything is packed: never a KeyError on an
+    entry the model was not built with."""
+    linear_fusion = bool(linear_fusion)
+    w = sd.get(prefix + "feature_aggreg.0.weight")
+    if w is None:
+        raise ValueError("%sfeature_aggreg.0.weight is missing: %s needs the roi_heads.box.* entries" % (prefix, who))
+    cin = int(w.shape[1])
+    has_compress = (prefix + "compress_dim_conv.0.weight") in sd
+    if cin == 2 * FPN_OUT and not has_compress:
+        trained = True
+    elif cin == FPN_OUT and has_compress:
+        trained = False
+    else:
+        raise ValueError("%sfeature_aggreg.0.weight has %d input channels and compress_dim_conv.0.weight is %s: neither a "
+                         "FEW_SHOT.LINEAR_FUSION True model (%d channels, no compress_dim_conv) nor a False one (%d, with it)"
+                         % (prefix, cin, "present" if has_compress else "absent", 2 * FPN_OUT, FPN_OUT))
+    if trained != linear_fusion:
+        raise ValueError("%sfeature_aggreg.0.weight has %d input channels and compress_dim_conv.0.weight is %s: the model was "
+                         "trained with FEW_SHOT.LINEAR_FUSION %s; build %s with linear_fusion=%r"
+                         % (prefix, cin, "present" if has_compress else "absent", trained, who, trained))
+    return linear_fusion
+
+
 def _bn(prefix, n, out):
     for k in ("weight", "bias", "running_mean", "running_var"):
         out[prefix + "." + k] = (n,)
@@ -214,25 +241,27 @@ def fcos_head_shapes(prefix="rpn.head."):
     return out
 
 
-def box_head_shapes(prefix="roi_heads.box.", box_cls_loss="ce_loss", soft_labeling=False):
+def box_head_shapes(prefix="roi_heads.box.", box_cls_loss="ce_loss", soft_labeling=False, linear_fusion=False):
     """Second-stage few-shot ROI box head keys (modeling/roi_heads/box_head/box_head.py:40-78: compress_dim_conv =
     Sequential(conv1x1, GN, LeakyReLU, conv1x1, GN, LeakyReLU) -> indices 0,1,3,4; feature_aggreg = Sequential(conv3x3,
     GN, LeakyReLU); fc6/fc7 make_fc; roi_box_predictors.py:37-99 FPNPredictor with 2 classes and 2x4 box deltas).
     box_cls_loss (FEW_SHOT.SECOND_STAGE_CLS_LOSS): cls_score has 2 outputs for 'ce_loss' and ONE for 'focal_loss' / 'mse_loss'
     (roi_box_predictors.py:47-50,66-68,76-77); bbox_pred keeps its 8.  soft_labeling (FEW_SHOT.SOFT_LABELING) admits 'l1_loss' (one
-    output) and 'cxe_loss' (two) and changes no shape by itself."""
+    output) and 'cxe_loss' (two) and changes no shape by itself.  linear_fusion (FEW_SHOT.LINEAR_FUSION, box_head.py:43,61-72): no
+    compress_dim_conv, and feature_aggreg.0 reads cat(x, query) = 2 * FPN_OUT channels."""
     out = OrderedDict()
     n_logits = box_cls_logits(box_cls_loss, soft_labeling)
     c2 = 2 * FPN_OUT
-    out[prefix + "compress_dim_conv.0.weight"] = (c2, c2, 1, 1)
-    out[prefix + "compress_dim_conv.0.bias"] = (c2,)
-    out[prefix + "compress_dim_conv.1.weight"] = (c2,)
-    out[prefix + "compress_dim_conv.1.bias"] = (c2,)
-    out[prefix + "compress_dim_conv.3.weight"] = (FPN_OUT, c2, 1, 1)
-    out[prefix + "compress_dim_conv.3.bias"] = (FPN_OUT,)
-    out[prefix + "compress_dim_conv.4.weight"] = (FPN_OUT,)
-    out[prefix + "compress_dim_conv.4.bias"] = (FPN_OUT,)
-    out[prefix + "feature_aggreg.0.weight"] = (FPN_OUT // 2, FPN_OUT, 3, 3)
+    if not linear_fusion:
+        out[prefix + "compress_dim_conv.0.weight"] = (c2, c2, 1, 1)
+        out[prefix + "compress_dim_conv.0.bias"] = (c2,)
+        out[prefix + "compress_dim_conv.1.weight"] = (c2,)
+        out[prefix + "compress_dim_conv.1.bias"] = (c2,)
+        out[prefix + "compress_dim_conv.3.weight"] = (FPN_OUT, c2, 1, 1)
+        out[prefix + "compress_dim_conv.3.bias"] = (FPN_OUT,)
+        out[prefix + "compress_dim_conv.4.weight"] = (FPN_OUT,)
+        out[prefix + "compress_dim_conv.4.bias"] = (FPN_OUT,)
+    out[prefix + "feature_aggreg.0.weight"] = (FPN_OUT // 2, c2 if linear_fusion else FPN_OUT, 3, 3)
     out[prefix + "feature_aggreg.0.bias"] = (FPN_OUT // 2,)
     out[prefix + "feature_aggreg.1.weight"] = (FPN_OUT // 2,)
     out[prefix + "feature_aggreg.1.bias"] = (FPN_OUT // 2,)
@@ -258,11 +287,11 @@ def hot_path_shapes(siamese_backbone=True):
     return out
 
 
-def full_model_shapes(siamese_backbone=True, box_cls_loss="ce_loss", soft_labeling=False):
+def full_model_shapes(siamese_backbone=True, box_cls_loss="ce_loss", soft_labeling=False, linear_fusion=False):
     """Hot path + second-stage box head = every state_dict entry of the reference model under the config of record
-    (siamese_backbone: see hot_path_shapes; box_cls_loss: see box_head_shapes)."""
+    (siamese_backbone: see hot_path_shapes; box_cls_loss, linear_fusion: see box_head_shapes)."""
     out = hot_path_shapes(siamese_backbone)
-    out.update(box_head_shapes(box_cls_loss=box_cls_loss, soft_labeling=soft_labeling))
+    out.update(box_head_shapes(box_cls_loss=box_cls_loss, soft_labeling=soft_labeling, linear_fusion=linear_fusion))
     return out
 
 

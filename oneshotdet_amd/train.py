@@ -33,6 +33,11 @@ soft_labeling / soft_labeling_func (FEW_SHOT.SOFT_LABELING / SOFT_LABELING_FUNC,
 only): every sampled ROI carries soft = f(IoU with its matched ground truth) (0 for background) from the sampler to the loss;
 "mse_loss" is then held against the soft labels, and "l1_loss" (one logit) and "cxe_loss" (two) exist.  "ce_loss" and "focal_loss"
 never read soft labels: with them the step makes the launches it makes without the option.
+
+linear_fusion (FEW_SHOT.LINEAR_FUSION, box_head.py:43,61-72,148; second_stage=True only): the box head in front of fc6 is ONE 3x3
+conv over cat(x, query), GroupNorm, LeakyReLU (no compress_dim_conv).  The conv is split at the concatenation into
+`feature_aggreg.0x` (ROI half) and `feature_aggreg.0q` (query half + bias), which state_dict() merges back into the reference's one
+512-channel `feature_aggreg.0.weight`.  False (the default) leaves the plan, the launches and the keys as they are.
 """
 import math
 import os
@@ -100,7 +105,9 @@ class TrainEngine(ForwardPass, BackwardPass, SecondStage, Update, State):
     def __init__(self, state_dict, dtype=torch.bfloat16, device="cuda", lr=0.0005, momentum=0.9, weight_decay=0.0001,
                  process_group=None, wgrad_side_stream=True, optimizer="fused", second_stage=False, ordered_wgrad=None,
                  exchange_single_rank=False, grad_wire_dtype=None, siamese_backbone=True, supp_roialign=True,
-                 center_sample=True, loc_loss_type="giou", box_cls_loss="ce_loss", soft_labeling=False, soft_labeling_func="linear"):
+                 center_sample=True, loc_loss_type="giou", box_cls_loss="ce_loss", soft_labeling=False, soft_labeling_func="linear",
+                 linear_fusion=False):
+        self.linear_fusion = bool(linear_fusion)
         self.center_sample, self.loc_loss_type = spec.loss_mode(center_sample, loc_loss_type)     # ValueError before anything is built
         self.soft_labeling, self.soft_labeling_func = spec.soft_labeling_mode(soft_labeling, soft_labeling_func)
         self.box_cls_loss = spec.box_cls_loss_mode(box_cls_loss, soft_labeling=self.soft_labeling)
@@ -301,7 +308,9 @@ class TrainEngine(ForwardPass, BackwardPass, SecondStage, Update, State):
         10 rows for 'ce_loss', 9 for the sigmoid losses).  Appended to the plan after the FCOS head:
         one more gradient bucket ('box_head')."""
         b = "roi_heads.box."
-        missing = [k for k in spec.box_head_shapes() if k not in sd]
+        if (b + "feature_aggreg.0.weight") in sd:
+            spec.check_linear_fusion(sd, self.linear_fusion, b)        # before anything is packed: never a KeyError on compress_dim_conv
+        missing = [k for k in spec.box_head_shapes(linear_fusion=self.linear_fusion) if k not in sd]
         if missing:
             raise KeyError("second_stage=True needs the roi_heads.box.* entries, e.g. %s" % missing[:2])
         spec.check_box_cls_score(sd, self.box_cls_loss, b, soft_labeling=self.soft_labeling)
@@ -313,13 +322,17 @@ class TrainEngine(ForwardPass, BackwardPass, SecondStage, Update, State):
             self._plan.append((name + ".weight", (cout, r, s, cin)))
             if has_bias:
                 self._plan.append((name + ".bias", (cout,)))
-        conv(b + "compress_dim_conv.0x", 2 * c, c, 1, 1, False)
-        conv(b + "compress_dim_conv.0q", 2 * c, c, 1, 1, True)
-        for gn_name in ("compress_dim_conv.1",):
-            self._plan += [(b + gn_name + ".weight", (2 * c,)), (b + gn_name + ".bias", (2 * c,))]
-        conv(b + "compress_dim_conv.3", c, 2 * c, 1, 1, True)
-        self._plan += [(b + "compress_dim_conv.4.weight", (c,)), (b + "compress_dim_conv.4.bias", (c,))]
-        conv(b + "feature_aggreg.0", mid, c, 3, 3, True)
+        if self.linear_fusion:                       # the 3x3 conv over cat(x, query), split like compress_dim_conv.0 below
+            conv(b + "feature_aggreg.0x", mid, c, 3, 3, False)
+            conv(b + "feature_aggreg.0q", mid, c, 3, 3, True)
+        else:
+            conv(b + "compress_dim_conv.0x", 2 * c, c, 1, 1, False)
+            conv(b + "compress_dim_conv.0q", 2 * c, c, 1, 1, True)
+            for gn_name in ("compress_dim_conv.1",):
+                self._plan += [(b + gn_name + ".weight", (2 * c,)), (b + gn_name + ".bias", (2 * c,))]
+            conv(b + "compress_dim_conv.3", c, 2 * c, 1, 1, True)
+            self._plan += [(b + "compress_dim_conv.4.weight", (c,)), (b + "compress_dim_conv.4.bias", (c,))]
+            conv(b + "feature_aggreg.0", mid, c, 3, 3, True)
         self._plan += [(b + "feature_aggreg.1.weight", (mid,)), (b + "feature_aggreg.1.bias", (mid,))]
         conv(b + "fc6", spec.BOX_MLP_DIM, mid * p * p, 1, 1, True)
         conv(b + "fc7", spec.BOX_MLP_DIM, spec.BOX_MLP_DIM, 1, 1, True)

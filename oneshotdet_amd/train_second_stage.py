@@ -39,25 +39,37 @@ class SecondStage(object):
                                                       spec.BOX_FG_IOU_THRESH, spec.BOX_REG_WEIGHTS)
         M = n * S
         slope, gr, eps = spec.BOX_LEAKY_SLOPE, spec.GN_GROUPS, spec.GN_EPS
-        (g0, dg0), (b0, db0) = self.extra[b + "compress_dim_conv.1.weight"], self.extra[b + "compress_dim_conv.1.bias"]
-        (g1, dg1), (b1, db1) = self.extra[b + "compress_dim_conv.4.weight"], self.extra[b + "compress_dim_conv.4.bias"]
+        linear = getattr(self, "linear_fusion", False)
         (g2, dg2), (b2, db2) = self.extra[b + "feature_aggreg.1.weight"], self.extra[b + "feature_aggreg.1.bias"]
-        c0x, c0q, c3, ca = (cv[b + k] for k in ("compress_dim_conv.0x", "compress_dim_conv.0q", "compress_dim_conv.3",
-                                                 "feature_aggreg.0"))
+        if linear:
+            # FEW_SHOT.LINEAR_FUSION (box_head.py:61-72,148): the split 3x3 conv takes the place of the split 1x1 conv, its
+            # GroupNorm is feature_aggreg.1 and nothing stands between it and fc6
+            c0x, c0q, pad0 = cv[b + "feature_aggreg.0x"], cv[b + "feature_aggreg.0q"], 1
+            (g0, dg0), (b0, db0) = (g2, dg2), (b2, db2)
+        else:
+            (g0, dg0), (b0, db0) = self.extra[b + "compress_dim_conv.1.weight"], self.extra[b + "compress_dim_conv.1.bias"]
+            (g1, dg1), (b1, db1) = self.extra[b + "compress_dim_conv.4.weight"], self.extra[b + "compress_dim_conv.4.bias"]
+            c0x, c0q, c3, ca = (cv[b + k] for k in ("compress_dim_conv.0x", "compress_dim_conv.0q", "compress_dim_conv.3",
+                                                     "feature_aggreg.0"))
+            pad0 = 0
         fc6, fc7, cp = cv[b + "fc6"], cv[b + "fc7"], cv[b + "pred"]
         # ---- forward
         qf1 = qfeats if shots == 1 else [q[::shots].contiguous() for q in qfeats]
         qs1 = [q_sizes[i * shots] for i in range(n)]
         uniform = len(set(qs1)) == 1
         q = bh.run_query_roi(qf1, qs1[0] if uniform else qs1, dt)                                # [N,7,7,C]
-        qh = ops.conv2d(q, c0q.pc)                                                               # W_q q + b
+        qh = ops.conv2d(q, c0q.pc, pad=pad0)                                                     # W_q q + b
         x = ops.roi_pool_levels(feats, spec.POOLER_SCALES, sb, sc, spec.BOX_POOL, spec.POOLER_SAMPLING_RATIO)
-        u0 = ops.conv2d(x, c0x.pc)
+        u0 = ops.conv2d(x, c0x.pc, pad=pad0)
         t0 = ops.groupnorm_act_rois(u0, g0, b0, gr, eps, slope, addend=qh, rois_per_add=S, add_stride=1, add_offset=0)
-        u1 = ops.conv2d(t0, c3.pc)
-        t1 = ops.groupnorm_act_rois(u1, g1, b1, gr, eps, slope)
-        u2 = ops.conv2d(t1, ca.pc, pad=1)
-        t2 = ops.groupnorm_act_rois(u2, g2, b2, gr, eps, slope)
+        u1 = t1 = u2 = d_u2 = d_t1 = d_u1 = None
+        if linear:
+            t2 = t0
+        else:
+            u1 = ops.conv2d(t0, c3.pc)
+            t1 = ops.groupnorm_act_rois(u1, g1, b1, gr, eps, slope)
+            u2 = ops.conv2d(t1, ca.pc, pad=1)
+            t2 = ops.groupnorm_act_rois(u2, g2, b2, gr, eps, slope)
         t2f = t2.view(M, 1, 1, -1)
         f6 = ops.conv2d(t2f, fc6.pc, act=ACT_RELU)
         f7 = ops.conv2d(f6, fc7.pc, act=ACT_RELU)
@@ -78,18 +90,21 @@ class SecondStage(object):
         d_f6 = dg(fc7, d_f7, mask=f6)
         wg(fc6, t2f, d_f6)
         d_t2 = dg(fc6, d_f6).view(t2.shape)
-        d_u2 = ops.groupnorm_act_rois_bwd(u2, g2, b2, d_t2, dg2, db2, gr, eps, slope)
-        wg(ca, t1, d_u2, pad=1)
-        d_t1 = dg(ca, d_u2)
-        d_u1 = ops.groupnorm_act_rois_bwd(u1, g1, b1, d_t1, dg1, db1, gr, eps, slope)
-        wg(c3, t0, d_u1)
-        d_t0 = dg(c3, d_u1)
+        if linear:
+            d_t0 = d_t2
+        else:
+            d_u2 = ops.groupnorm_act_rois_bwd(u2, g2, b2, d_t2, dg2, db2, gr, eps, slope)
+            wg(ca, t1, d_u2, pad=1)
+            d_t1 = dg(ca, d_u2)
+            d_u1 = ops.groupnorm_act_rois_bwd(u1, g1, b1, d_t1, dg1, db1, gr, eps, slope)
+            wg(c3, t0, d_u1)
+            d_t0 = dg(c3, d_u1)
         d_u0 = ops.groupnorm_act_rois_bwd(u0, g0, b0, d_t0, dg0, db0, gr, eps, slope, addend=qh, rois_per_add=S, add_stride=1,
                                           add_offset=0)
-        wg(c0x, x, d_u0)
+        wg(c0x, x, d_u0, pad=pad0)
         d_x = dg(c0x, d_u0)
         d_qh = ops.rois_sum(d_u0, n, S)                     # the query half was added to every ROI of its image
-        wg(c0q, q, d_qh)
+        wg(c0q, q, d_qh, pad=pad0)
         d_q = dg(c0q, d_qh)
         gx = ops.roi_pool_levels_bwd([(f.shape[1], f.shape[2]) for f in feats], spec.POOLER_SCALES, sb, sc, d_x, spec.BOX_POOL,
                                      spec.POOLER_SAMPLING_RATIO)

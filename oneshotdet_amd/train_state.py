@@ -31,8 +31,8 @@ class State(object):
                                  lambda v, keys=keys: {keys[0]: v[0:1].permute(0, 3, 1, 2), keys[1]: v[1:2].permute(0, 3, 1, 2)})
                 else:
                     out[name] = (keys, lambda ts: torch.cat(ts, 0), lambda v, keys=keys: {keys[0]: v[0:1], keys[1]: v[1:2]})
-            elif base in (b + "compress_dim_conv.0x", b + "compress_dim_conv.0q"):
-                key = b + "compress_dim_conv.0." + leaf
+            elif base in (b + "compress_dim_conv.0x", b + "compress_dim_conv.0q", b + "feature_aggreg.0x", b + "feature_aggreg.0q"):
+                key = base[:-1] + "." + leaf            # the two halves of ONE reference conv (FEW_SHOT.LINEAR_FUSION: the 3x3 one)
                 if leaf == "bias":
                     out[name] = ([key], lambda ts: ts[0], lambda v, key=key: {key: v})
                 else:
