@@ -41,6 +41,9 @@ def main():
                          "the sigmoid losses have one class logit and a sigmoid score")
     ap.add_argument("--linear-fusion", action="store_true",
                     help="the model was trained with FEW_SHOT.LINEAR_FUSION: no compress_dim_conv, a 512-channel feature_aggreg.0")
+    ap.add_argument("--neg-support", action="store_true",
+                    help="the model was trained with a negative support (FEW_SHOT.NEG_SUPPORT; 'ce_loss', no --linear-fusion): "
+                         "validated, detection itself does not change")
     args = ap.parse_args()
     siamese = not args.shared_backbone
     roialign = not args.no_supp_roialign
@@ -70,7 +73,8 @@ def main():
         print("synthetic weights (no checkpoint given)")
     det = modules.OneShotDetector(sd, dtype=torch.bfloat16 if args.dtype == "bf16" else torch.float32, siamese_backbone=siamese,
                                   supp_roialign=roialign, box_cls_loss=args.box_cls_loss, soft_labeling=args.soft_labeling,
-                                  linear_fusion=args.linear_fusion and not args.first_stage_only)
+                                  linear_fusion=args.linear_fusion and not args.first_stage_only,
+                                  neg_support=args.neg_support and not args.first_stage_only)
     # two targets and two queries of different sizes
     targets = [torch.from_numpy(synth.make_images("ex.t%d" % i, 1, h, w)[0]) for i, (h, w) in enumerate([(480, 640), (512, 384)])]
     queries = [torch.from_numpy(synth.make_images("ex.q%d" % i, 1, h, w)[0]) for i, (h, w) in enumerate([(127, 127), (96, 160)])]

@@ -74,9 +74,16 @@ def main():
                     help="soft label as a function of the IoU (FEW_SHOT.SOFT_LABELING_FUNC)")
     ap.add_argument("--linear-fusion", action="store_true",
                     help="box head: one 3x3 conv over cat(x, query) in front of fc6, no compress_dim_conv (FEW_SHOT.LINEAR_FUSION)")
+    ap.add_argument("--neg-support", action="store_true",
+                    help="second stage: score the sampled ROIs against a support of another category too and add the margin loss "
+                         "loss_cls_suppress (FEW_SHOT.NEG_SUPPORT; 'ce_loss', one shot, no --linear-fusion).  The reference ships no "
+                         "rule for choosing the negative support (its dataset's negative category is always -1); this example's own "
+                         "rule: sample i's negative support is the support crop of sample (i + 1) mod batch")
     args = ap.parse_args()
     if not args.first_stage_only:
         spec.box_cls_loss_mode(args.box_cls_loss, soft_labeling=args.soft_labeling)      # l1_loss / cxe_loss without --soft-labeling: refused here
+    neg_support = spec.check_neg_support(args.neg_support, not args.first_stage_only, args.linear_fusion, args.box_cls_loss,
+                                         args.soft_labeling, who="the example")
     siamese = not args.shared_backbone
     roialign = not args.no_supp_roialign
     center_sample = not args.no_center_sample
@@ -91,7 +98,7 @@ def main():
                                  supp_roialign=roialign, center_sample=center_sample, loc_loss_type=args.loc_loss_type,
                                  box_cls_loss=args.box_cls_loss, soft_labeling=args.soft_labeling,
                                  soft_labeling_func=args.soft_labeling_func,
-                                 linear_fusion=args.linear_fusion and not args.first_stage_only)
+                                 linear_fusion=args.linear_fusion and not args.first_stage_only, neg_support=neg_support)
     start = 0
     last = os.path.join(args.out, "last_checkpoint")
     if args.resume and os.path.exists(last):
@@ -101,7 +108,8 @@ def main():
                                                 box_cls_loss=None if args.first_stage_only else args.box_cls_loss,
                                                 soft_labeling=None if args.first_stage_only else args.soft_labeling,
                                                 soft_labeling_func=None if args.first_stage_only else args.soft_labeling_func,
-                                                linear_fusion=None if args.first_stage_only else args.linear_fusion)
+                                                linear_fusion=None if args.first_stage_only else args.linear_fusion,
+                                                neg_support=None if args.first_stage_only else neg_support)
         print("resumed at iteration", start)
     else:
         eng = make_engine(synth.make_state_dict(shapes))      # or checkpoint.load_checkpoint / load_c2_resnet, see detect.py
@@ -131,15 +139,19 @@ def main():
             imgs.append(dimg); supps.append(supp); targets.append(tgt)
         images = T.collate(imgs, spec.SIZE_DIVISIBILITY, stem_dtype=dtype)
         queries = T.collate(supps, spec.SIZE_DIVISIBILITY, stem_dtype=dtype)
+        # the same crops rotated by one: the same padded shape as `queries`, which the engine requires
+        neg_queries = T.collate(supps[1:] + supps[:1], spec.SIZE_DIVISIBILITY, stem_dtype=dtype) if neg_support else None
         g = max(len(t) for t in targets)
         gt = torch.zeros(args.batch, g, 4)
         for i, t in enumerate(targets):
             gt[i, :len(t)] = t.bbox
         cnt = torch.tensor([len(t) for t in targets], dtype=torch.int32)
-        losses = eng.train_step(images, queries, gt.cuda(), cnt.cuda())
+        losses = eng.train_step(images, queries, gt.cuda(), cnt.cuda(), neg_queries=neg_queries)
         if rank == 0 and (it % 5 == 0 or it + 1 == args.iters):
             l = losses.float().cpu()
             extra = "" if eng.box_losses is None else "  loss_classifier %.4f  loss_box_reg %.4f" % tuple(eng.box_losses[:2].float().cpu())
+            if eng.box_suppress_loss is not None:
+                extra += "  loss_cls_suppress %.4f" % float(eng.box_suppress_loss[0])
             print("iter %4d  loss_cls %.4f  loss_reg %.4f  loss_centerness %.4f  (%d positives)%s"
                   % (it, l[0], l[1], l[2], int(l[3]), extra))
         if rank == 0 and ((it + 1) % args.checkpoint_period == 0 or it + 1 == args.iters):

@@ -144,6 +144,11 @@ SIGNATURES_SOFT_LABELS = {
     "osd_box_loss_soft": (_i, [_p, _p, _p, _p, _i, _i, _i, _f, _f, _p, _p, _i, _i, _p, _i, _p]),
 }
 
+# include/oneshotdet_hip_neg_support.h: the second stage's negative support (FEW_SHOT.NEG_SUPPORT), a fourth table
+SIGNATURES_NEG_SUPPORT = {
+    "osd_box_loss_neg_support": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _f, _f, _f, _f, _p, _p, _p, _i, _i, _p]),
+}
+
 _lib = None
 
 
@@ -162,7 +167,8 @@ def load():
                        "__graft_entry__.build(); there is no CPU/eager fallback" % LIB_PATH)
     import torch  # noqa: F401  (loads libamdhip64 first)
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_BOX_MODES.items()) + list(SIGNATURES_SOFT_LABELS.items()):
+    for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_BOX_MODES.items()) + list(SIGNATURES_SOFT_LABELS.items())
+                              + list(SIGNATURES_NEG_SUPPORT.items())):
         fn = getattr(lib, name)   # AttributeError if the symbol is missing
         fn.restype = res
         fn.argtypes = args

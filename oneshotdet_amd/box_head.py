@@ -23,7 +23,10 @@ from .ops import ACT_NONE, ACT_RELU, PackedConv
 class BoxHeadWeights(object):
     """Packed `roi_heads.box.*` (spec.box_head_shapes)."""
 
-    def __init__(self, sd, dtype, prefix="roi_heads.box.", box_cls_loss="ce_loss", soft_labeling=False, linear_fusion=False):
+    def __init__(self, sd, dtype, prefix="roi_heads.box.", box_cls_loss="ce_loss", soft_labeling=False, linear_fusion=False,
+                 neg_support=False):
+        # FEW_SHOT.NEG_SUPPORT: validated (ValueError by name) and otherwise nothing: inference discards the negative branch
+        self.neg_support = spec.check_neg_support(neg_support, True, linear_fusion, box_cls_loss, soft_labeling, who="the box head")
         self.soft_labeling = bool(soft_labeling)
         self.linear_fusion = spec.check_linear_fusion(sd, linear_fusion, prefix)        # before anything is packed
         self.box_cls_loss = spec.box_cls_loss_mode(box_cls_loss, soft_labeling=self.soft_labeling)

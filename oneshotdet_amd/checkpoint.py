@@ -141,7 +141,7 @@ def save_training_checkpoint(path, engine, iteration, tag_last=True):
     only record of it: the pooling has no weights); `center_sample` / `loc_loss_type` the FCOS loss it trained with (likewise);
     `box_cls_loss` the second stage's classification loss (the two one-logit losses have the same shapes); `soft_labeling` /
     `soft_labeling_func` the soft labels it was held against (no weights either); `linear_fusion` the box head's layout (the key set
-    shows it too)."""
+    shows it too); `neg_support` whether it trained with a negative support (FEW_SHOT.NEG_SUPPORT: no weights, no keys)."""
     return save_checkpoint(path, engine.state_dict(), tag_last=tag_last, optimizer=engine.optimizer_state_dict(),
                            iteration=int(iteration), siamese_backbone=bool(getattr(engine, "siamese_backbone", True)),
                            supp_roialign=bool(getattr(engine, "supp_roialign", True)),
@@ -150,7 +150,8 @@ def save_training_checkpoint(path, engine, iteration, tag_last=True):
                            box_cls_loss=str(getattr(engine, "box_cls_loss", spec.BOX_CLS_LOSS)),
                            soft_labeling=bool(getattr(engine, "soft_labeling", spec.SOFT_LABELING)),
                            soft_labeling_func=str(getattr(engine, "soft_labeling_func", spec.SOFT_LABELING_FUNC)),
-                           linear_fusion=bool(getattr(engine, "linear_fusion", spec.LINEAR_FUSION)))
+                           linear_fusion=bool(getattr(engine, "linear_fusion", spec.LINEAR_FUSION)),
+                           neg_support=bool(getattr(engine, "neg_support", spec.NEG_SUPPORT)))
 
 
 def _loss_name(mode):
@@ -159,7 +160,7 @@ def _loss_name(mode):
 
 
 def resume_training(path, make_engine, siamese_backbone=None, supp_roialign=None, center_sample=None, loc_loss_type=None,
-                    box_cls_loss=None, soft_labeling=None, soft_labeling_func=None, linear_fusion=None):
+                    box_cls_loss=None, soft_labeling=None, soft_labeling_func=None, linear_fusion=None, neg_support=None):
     """Load a checkpoint written by save_training_checkpoint: make_engine(state_dict) -> TrainEngine; its momentum and
     step count are restored.  Returns (engine, iteration).  The file's mode (recorded by save_training_checkpoint; for
     older files: whether it holds `supp_backbone.*`) must be the engine's: a resumed run never ties or unties weights
@@ -171,8 +172,15 @@ def resume_training(path, make_engine, siamese_backbone=None, supp_roialign=None
     expectation (None: whatever the file holds), a file without the field was trained with "ce_loss".  And for the soft labels:
     soft_labeling / soft_labeling_func are the caller's expectations (None: whatever the file holds), a file without the fields was
     trained with (False, "linear"); the function only matters where soft labels are on.  And for the box head's layout:
-    linear_fusion is the caller's expectation (None: whatever the file holds), a file without the field was trained with False."""
+    linear_fusion is the caller's expectation (None: whatever the file holds), a file without the field was trained with False.
+    And for the negative support: neg_support is the caller's expectation (None: whatever the file holds), a file without the field
+    was trained with False."""
     data = _read(path)
+    neg = data.get("neg_support")
+    neg = spec.NEG_SUPPORT if neg is None else bool(neg)
+    if neg_support is not None and bool(neg_support) != neg:
+        raise ValueError("%s was trained with neg_support=%r (FEW_SHOT.NEG_SUPPORT); resuming it with neg_support=%r would continue "
+                         "the run on another objective: build the engine with neg_support=%r" % (path, neg, bool(neg_support), neg))
     fusion = data.get("linear_fusion")
     fusion = spec.LINEAR_FUSION if fusion is None else bool(fusion)
     if linear_fusion is not None and bool(linear_fusion) != fusion:
@@ -213,6 +221,10 @@ def resume_training(path, make_engine, siamese_backbone=None, supp_roialign=None
                             bool(siamese_backbone)))
     sd, extras = load_checkpoint(path, siamese_backbone=mode, box_cls_loss=box, soft_labeling=soft[0], linear_fusion=fusion)
     eng = make_engine(sd)
+    built_neg = bool(getattr(eng, "neg_support", spec.NEG_SUPPORT))
+    if built_neg != neg:
+        raise ValueError("%s was trained with neg_support=%r (FEW_SHOT.NEG_SUPPORT) but make_engine built an engine with "
+                         "neg_support=%r" % (path, neg, built_neg))
     built_fusion = bool(getattr(eng, "linear_fusion", spec.LINEAR_FUSION))
     if built_fusion != fusion:
         raise ValueError("%s was trained with linear_fusion=%r (FEW_SHOT.LINEAR_FUSION) but make_engine built an engine with "

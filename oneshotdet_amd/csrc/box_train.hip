@@ -11,6 +11,7 @@
 #include "osd_common.h"
 #include "../../include/oneshotdet_hip_box_modes.h"
 #include "../../include/oneshotdet_hip_soft_labels.h"
+#include "../../include/oneshotdet_hip_neg_support.h"
 
 namespace {
 
@@ -305,18 +306,23 @@ __device__ __forceinline__ float box_focal_grad(float x, int label, float gamma,
 //   OSD_BOX_CLS_L1     L = 1, loss.py:364-365: mean over the [M,M] broadcast of |s_i - t_j|, which has no closed form: the valid rows'
 //                      soft labels go through LDS in tiles of kL1Tile rows and every thread walks every tile for its rows
 //   OSD_BOX_CLS_CXE    L = 2, loss.py:294-296,366-367: -mean([1 - t, t] * log softmax) over the [M,2] tensor, i.e. over 2M elements
+// With FEW_SHOT.NEG_SUPPORT (include/oneshotdet_hip_neg_support.h; NEG, 'ce_loss' only) `pred_neg` holds the same rows scored against the
+// negative support and loss.py:435-444 is added over the K valid rows with label 1: relu(q - p + margin).mean(), p / q = the softmax
+// score of column 1 of pred / pred_neg.  K is counted before the first gradient is written; K == 0 gives 0 (the reference: NaN).
 // The smooth-L1 term, the reduction, the NaN poisoning of labels > 1 and the zeroing of invalid rows are one chain for all modes.
 constexpr int kBoxClsSoftMse = 100;      // OSD_BOX_CLS_MSE of osd_box_loss_soft
 constexpr int kL1Tile = 1024;            // soft labels staged per trip: 4 KB of LDS next to the 8 KB of the reduction
 
-template <typename T, int MODE>
+template <typename T, int MODE, bool NEG = false>
 __device__ __forceinline__ void box_loss_body(const T* __restrict__ pred, const int32_t* __restrict__ labels,
                                               const float* __restrict__ targets, const int32_t* __restrict__ s_count,
                                               int n_img, int S, int pstride, float w_cls, float w_box, float gamma, float alpha,
                                               float* __restrict__ losses, T* __restrict__ d_pred, int gstride,
-                                              const float* __restrict__ soft = nullptr) {
+                                              const float* __restrict__ soft = nullptr, const T* __restrict__ pred_neg = nullptr,
+                                              T* __restrict__ d_pred_neg = nullptr, float margin = 0.f, float w_sup = 0.f) {
+  static_assert(!NEG || MODE == OSD_BOX_CLS_CE, "NEG_SUPPORT is defined for 'ce_loss' only");
   constexpr int L = (MODE == OSD_BOX_CLS_CE || MODE == OSD_BOX_CLS_CXE) ? 2 : 1;
-  __shared__ float red[2][1024];
+  __shared__ float red[NEG ? 3 : 2][1024];
   __shared__ int nval, bad_label, npos_all;
   const int t = threadIdx.x;
   if (t == 0) {
@@ -361,12 +367,28 @@ __device__ __forceinline__ void box_loss_body(const T* __restrict__ pred, const 
     ml = red[0][0] * inv_n;
     __syncthreads();                       // red[] is written again below
   }
+  float inv_k = 0.f, ls = 0.f;            // 1 / K, 0 for K == 0 (suppress loss and gradients 0); the hinge sum of this thread's rows
+  if constexpr (NEG) {
+    int c = 0;
+    for (int r = t; r < M; r += 1024) {
+      const int img = r / S, ri = r - img * S;
+      c += (ri < min(s_count[img], S) && labels[r] == 1) ? 1 : 0;
+    }
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) c += __shfl_xor(c, d, 64);
+    if ((t & 63) == 0 && c) atomicAdd(&npos_all, c);
+    __syncthreads();
+    inv_k = npos_all > 0 ? 1.f / (float)npos_all : 0.f;
+  }
   float lc = 0.f, lb = 0.f;
   for (int r = t; r < M; r += 1024) {
     const int img = r / S, ri = r - img * S;
     const bool valid = ri < min(s_count[img], S);
     T* g = d_pred ? d_pred + (size_t)r * gstride : nullptr;
     if (g) for (int q = 0; q < gstride; ++q) g[q] = from_f32<T>(0.f);
+    if constexpr (NEG) {                   // the data-gradient conv reads the whole row of both branches
+      if (g) for (int q = 0; q < gstride; ++q) d_pred_neg[(size_t)r * gstride + q] = from_f32<T>(0.f);
+    }
     if (!valid) continue;
     const T* p = pred + (size_t)r * pstride;
     // two classes (background / the queried object: ROI_BOX_HEAD.NUM_CLASSES = 2 in the config of record); a row is
@@ -380,10 +402,35 @@ __device__ __forceinline__ void box_loss_body(const T* __restrict__ pred, const 
       const float e0 = expf(x0 - m), e1 = expf(x1 - m);
       const float lse = m + logf(e0 + e1);
       lc += lse - (l == 1 ? x1 : x0);
+      const float s0 = e0 / (e0 + e1), s1 = e1 / (e0 + e1);
+      float hp = 0.f;                      // d(w_sup * suppress) / d x0 of this row; d / d x1 is its negative
+      if constexpr (NEG) {
+        if (l == 1) {
+          const T* pn = pred_neg + (size_t)r * pstride;
+          const float y0 = to_f32(pn[0]), y1 = to_f32(pn[1]);
+          const float mn = fmaxf(y0, y1);
+          const float f0 = expf(y0 - mn), f1 = expf(y1 - mn);
+          const float q0 = f0 / (f0 + f1), q1 = f1 / (f0 + f1);
+          const float h = q1 - s1 + margin;
+          if (h > 0.f) {                   // d p / d x1 = p (1 - p) = s0 s1, d p / d x0 = -s0 s1; the same for q
+            ls += h;
+            hp = w_sup * inv_k * (s0 * s1);
+            if (g) {
+              T* gn = d_pred_neg + (size_t)r * gstride;
+              gn[0] = from_f32<T>(-(w_sup * inv_k * (q0 * q1)));
+              gn[1] = from_f32<T>(w_sup * inv_k * (q0 * q1));
+            }
+          }
+        }
+      }
       if (g) {
-        const float s0 = e0 / (e0 + e1), s1 = e1 / (e0 + e1);
-        g[0] = from_f32<T>(w_cls * inv_n * (s0 - (l == 0 ? 1.f : 0.f)));
-        g[1] = from_f32<T>(w_cls * inv_n * (s1 - (l == 1 ? 1.f : 0.f)));
+        if constexpr (NEG) {
+          g[0] = from_f32<T>(w_cls * inv_n * (s0 - (l == 0 ? 1.f : 0.f)) + hp);
+          g[1] = from_f32<T>(w_cls * inv_n * (s1 - (l == 1 ? 1.f : 0.f)) - hp);
+        } else {
+          g[0] = from_f32<T>(w_cls * inv_n * (s0 - (l == 0 ? 1.f : 0.f)));
+          g[1] = from_f32<T>(w_cls * inv_n * (s1 - (l == 1 ? 1.f : 0.f)));
+        }
       }
     } else if constexpr (MODE == OSD_BOX_CLS_FOCAL) {
       const float x = to_f32(p[0]);
@@ -468,9 +515,13 @@ __device__ __forceinline__ void box_loss_body(const T* __restrict__ pred, const 
   }
   red[0][t] = lc;
   red[1][t] = lb;
+  if constexpr (NEG) red[2][t] = ls;
   __syncthreads();
   for (int s = 512; s > 0; s >>= 1) {
-    if (t < s) { red[0][t] += red[0][t + s]; red[1][t] += red[1][t + s]; }
+    if (t < s) {
+      red[0][t] += red[0][t + s]; red[1][t] += red[1][t + s];
+      if constexpr (NEG) red[2][t] += red[2][t + s];
+    }
     __syncthreads();
   }
   if (t == 0) {
@@ -489,6 +540,10 @@ __device__ __forceinline__ void box_loss_body(const T* __restrict__ pred, const 
       losses[0] = w_cls * red[0][0] * inv_n * 0.5f + poison;                // 5 * CXE: the mean runs over the 2M elements of [M,2]
     losses[1] = w_box * red[1][0] * inv_n + poison;     // 2.5 * smooth_l1(sum) / labels.numel()
     losses[2] = (float)nval;
+    if constexpr (NEG) {
+      losses[3] = w_sup * red[2][0] * inv_k + poison;   // 2.5 * relu(q - p + 0.3).mean() over the K foreground rows
+      losses[4] = (float)npos_all;
+    }
   }
 }
 
@@ -509,6 +564,18 @@ __global__ void __launch_bounds__(1024) box_loss_mode_kernel(const T* __restrict
                                                              float alpha, float* __restrict__ losses, T* __restrict__ d_pred,
                                                              int gstride) {
   box_loss_body<T, MODE>(pred, labels, targets, s_count, n_img, S, pstride, w_cls, w_box, gamma, alpha, losses, d_pred, gstride);
+}
+
+// 'ce_loss' with a negative support (osd_box_loss_neg_support)
+template <typename T>
+__global__ void __launch_bounds__(1024) box_loss_neg_kernel(const T* __restrict__ pred, const T* __restrict__ pred_neg,
+                                                            const int32_t* __restrict__ labels, const float* __restrict__ targets,
+                                                            const int32_t* __restrict__ s_count, int n_img, int S, int pstride,
+                                                            float w_cls, float w_box, float margin, float w_sup,
+                                                            float* __restrict__ losses, T* __restrict__ d_pred,
+                                                            T* __restrict__ d_pred_neg, int gstride) {
+  box_loss_body<T, OSD_BOX_CLS_CE, true>(pred, labels, targets, s_count, n_img, S, pstride, w_cls, w_box, 0.f, 0.f, losses, d_pred, gstride,
+                                         nullptr, pred_neg, d_pred_neg, margin, w_sup);
 }
 
 // the soft-label modes (osd_box_loss_soft)
@@ -882,6 +949,31 @@ extern "C" int osd_box_loss(const void* pred, const int32_t* labels, const float
                             int grad_stride, int dtype, void* stream) {
   return box_loss_launch("box_loss", pred, labels, targets, s_count, n, rois_per_image, pred_stride, w_cls, w_box, losses, d_pred,
                          grad_stride, dtype, nullptr, OSD_BOX_CLS_CE, 0.f, 0.f, stream);
+}
+
+extern "C" int osd_box_loss_neg_support(const void* pred, const void* pred_neg, const int32_t* labels, const float* targets,
+                                        const int32_t* s_count, int n, int rois_per_image, int pred_stride, float w_cls, float w_box,
+                                        float margin, float w_suppress, float* losses, void* d_pred, void* d_pred_neg,
+                                        int grad_stride, int dtype, void* stream) {
+  if (!pred || !pred_neg || !labels || !targets || !s_count || !losses)
+    return osd_fail(OSD_ERR_INVALID_ARG, "box_loss_neg_support: null argument");
+  if ((d_pred == nullptr) != (d_pred_neg == nullptr))
+    return osd_fail(OSD_ERR_INVALID_ARG, "box_loss_neg_support: d_pred and d_pred_neg are given together or not at all");
+  if (pred_stride < 2 + 8 || (d_pred && grad_stride < 2 + 8))
+    return osd_fail(OSD_ERR_INVALID_ARG, "box_loss_neg_support: 2 logits + 8 deltas per row");
+  const dim3 grid(1), block(1024);
+  hipStream_t st = OSD_STREAM(stream);
+  if (dtype == OSD_F32)
+    hipLaunchKernelGGL(box_loss_neg_kernel<float>, grid, block, 0, st, (const float*)pred, (const float*)pred_neg, labels, targets,
+                       s_count, n, rois_per_image, pred_stride, w_cls, w_box, margin, w_suppress, losses, (float*)d_pred,
+                       (float*)d_pred_neg, grad_stride);
+  else if (dtype == OSD_BF16)
+    hipLaunchKernelGGL(box_loss_neg_kernel<__bf16>, grid, block, 0, st, (const __bf16*)pred, (const __bf16*)pred_neg, labels, targets,
+                       s_count, n, rois_per_image, pred_stride, w_cls, w_box, margin, w_suppress, losses, (__bf16*)d_pred,
+                       (__bf16*)d_pred_neg, grad_stride);
+  else
+    return osd_fail(OSD_ERR_INVALID_ARG, "box_loss_neg_support: bad dtype");
+  return osd_check_launch("box_loss_neg_support");
 }
 
 extern "C" int osd_groupnorm_act_rois_bwd(const void* x, const void* addend, const float* gamma, const float* beta,

@@ -375,11 +375,15 @@ class HotPathEngine(object):
     reads no soft label.
     linear_fusion (FEW_SHOT.LINEAR_FUSION, box_head.py:43,61-72): the second stage's head in front of fc6 is one 3x3 conv over
     cat(x, query), GroupNorm, LeakyReLU; the state_dict has no compress_dim_conv.* and a 512-channel feature_aggreg.0.  A state_dict
-    trained with the other setting is refused (ValueError naming the option)."""
+    trained with the other setting is refused (ValueError naming the option).
+    neg_support (FEW_SHOT.NEG_SUPPORT.TURN_ON): how the model was trained; validated against the combinations the option exists in
+    ('ce_loss', no linear_fusion) and changes nothing computed: the reference computes the negative logits in evaluation and discards
+    them (box_head.py:156-161,175-177), and the state_dict has the plain 'ce_loss' model's keys and shapes."""
 
     def __init__(self, state_dict, dtype=torch.float32, device="cuda", siamese_backbone=True, supp_roialign=True,
-                 box_cls_loss="ce_loss", soft_labeling=False, soft_labeling_func="linear", linear_fusion=False):
+                 box_cls_loss="ce_loss", soft_labeling=False, soft_labeling_func="linear", linear_fusion=False, neg_support=False):
         self.linear_fusion = bool(linear_fusion)
+        self.neg_support = spec.check_neg_support(neg_support, True, linear_fusion, box_cls_loss, soft_labeling, who="the HotPathEngine")
         self.soft_labeling, self.soft_labeling_func = spec.soft_labeling_mode(soft_labeling, soft_labeling_func)
         self.box_cls_loss = spec.box_cls_loss_mode(box_cls_loss, soft_labeling=self.soft_labeling)    # ValueError before anything is built
         if not torch.cuda.is_available():
@@ -408,7 +412,7 @@ class HotPathEngine(object):
         if all(k in self.sd for k in spec.box_head_shapes(linear_fusion=self.linear_fusion)):
             from .box_head import BoxHeadWeights
             self.box_head = BoxHeadWeights(self.sd, self.dtype, box_cls_loss=self.box_cls_loss, soft_labeling=self.soft_labeling,
-                                           linear_fusion=self.linear_fusion)
+                                           linear_fusion=self.linear_fusion, neg_support=self.neg_support)
 
     def tune(self, images, queries, second_stage=False):
         """Pick, by measurement on this device, the conv algorithm (kernel generation, ring depth, tile) for every

@@ -1390,6 +1390,33 @@ def box_loss(pred, labels, targets, s_count, n, rois_per_image, w_cls, w_box, gr
     return losses, d
 
 
+def box_loss_neg_support(pred, pred_neg, labels, targets, s_count, n, rois_per_image, w_cls, w_box,
+                         w_suppress=spec.BOX_SUPPRESS_WEIGHT, margin=spec.BOX_SUPPRESS_MARGIN, grad_stride=0, d_out=None):
+    """box_loss for 'ce_loss' with FEW_SHOT.NEG_SUPPORT (loss.py:435-444; osd_box_loss_neg_support).  pred / pred_neg [M, stride]:
+    the sampled rows scored against the support and against the negative support (2 logits, then 8 deltas) -> losses [5] =
+    (classification, box regression, valid rows, w_suppress * relu(q - p + margin).mean() over the K valid rows with label 1, K),
+    p / q the softmax scores of column 1, and, with grad_stride, d_pred and d_pred_neg [M, grad_stride] (else None, None).
+    K == 0 gives a suppress loss of 0 (the reference: NaN).  d_out [2M, grad_stride] (optional): the buffer the two gradients are
+    written to, d_pred in its first M rows and d_pred_neg behind them (the stacked rows of the two-branch trunk)."""
+    m = n * rois_per_image
+    pred2, neg2 = pred.reshape(m, -1), pred_neg.reshape(m, -1)
+    if neg2.shape != pred2.shape or neg2.dtype != pred2.dtype or neg2.device != pred2.device:
+        raise ValueError("box_loss_neg_support: pred_neg must have pred's shape, dtype and device")
+    pred2, neg2 = pred2.contiguous(), neg2.contiguous()
+    losses = torch.empty((5,), device=pred.device, dtype=torch.float32)
+    d = dn = None
+    if grad_stride:
+        if d_out is None:
+            d_out = torch.empty((2 * m, grad_stride), device=pred.device, dtype=pred.dtype)
+        assert d_out.shape == (2 * m, grad_stride) and d_out.dtype == pred.dtype and d_out.is_contiguous()
+        d, dn = d_out[:m], d_out[m:]
+    _lib.call("osd_box_loss_neg_support", _p(pred2), _p(neg2), _p(labels), _p(targets), _p(s_count), n, rois_per_image,
+              pred2.shape[1], float(w_cls), float(w_box), float(margin), float(w_suppress), _p(losses), _p(d), _p(dn),
+              int(grad_stride), _dt(pred), _stream())
+    _rec("box_loss_neg_support", pred=pred2, pred_neg=neg2, losses=losses, d_pred=d, d_pred_neg=dn)
+    return losses, d, dn
+
+
 def groupnorm_act_rois_bwd(x, gamma, beta, dy, dgamma, dbeta, groups=32, eps=1e-5, slope=0.2, addend=None, rois_per_add=1,
                            add_stride=1, add_offset=0):
     """Backward of groupnorm_act_rois: -> dx; dgamma / dbeta [C] fp32 accumulated."""

@@ -70,6 +70,9 @@ SOFT_LABELING_FUNC = "linear"          # FEW_SHOT.SOFT_LABELING_FUNC (box_head/l
 SOFT_LABELING_FUNCS = ("discrete", "linear", "transLinear", "trans4thLinear")     # index = OSD_SOFT_LABEL_* of include/oneshotdet_hip_soft_labels.h
 BOX_CLS_LOSSES_SOFT = tuple(m for m, row in BOX_CLS_MODES.items() if row.soft_only)      # l1, cxe: only with SOFT_LABELING
 LINEAR_FUSION = False                  # defaults.py FEW_SHOT.LINEAR_FUSION: one 3x3 conv over cat(x, query) in front of fc6 (box_head.py:43,61-72,148)
+NEG_SUPPORT = False                    # defaults.py FEW_SHOT.NEG_SUPPORT.TURN_ON: the sampled ROIs are also scored against a support of another category (box_head.py:128-139)
+BOX_SUPPRESS_MARGIN = 0.3              # box_head/loss.py:442: relu(q - p + 0.3).mean() over the foreground rows
+BOX_SUPPRESS_WEIGHT = 2.5              # box_head.py:188: loss_cls_suppress = cls_suppress * 2.5
 BOX_LOSS_ALPHA = 0.25                 # FEW_SHOT.SECOND_STAGE_LOSS_ALPHA (defaults.py:512); gamma is FCOS.LOSS_GAMMA (box_head/loss.py:40-44)
 LEVEL_MAP_SCALE = 224                 # poolers.py:16 LevelMapper canonical_scale / canonical_level / eps
 LEVEL_MAP_LEVEL = 4
@@ -110,12 +113,14 @@ def box_cls_decode_mode(box_cls_loss, soft_labeling=False):
 def box_cls_loss_mode(box_cls_loss, loss_weighted=False, neg_support=False, method="concat", soft_labeling=False):
     """-> the validated FEW_SHOT.SECOND_STAGE_CLS_LOSS name; ValueError for a loss box_head/loss.py:343-369 does not have and, by
     name, for what it has that this build does not support: FEW_SHOT.LOSS_WEIGHTED (its reference path
-    calls .cuda() unconditionally, loss.py:349-357: nothing to record it against), negative support and SECOND_STAGE_METHOD 'rn'.
+    calls .cuda() unconditionally, loss.py:349-357: nothing to record it against), SECOND_STAGE_METHOD 'rn', and negative support
+    (FEW_SHOT.NEG_SUPPORT) with any loss but 'ce_loss' (the margin loss of loss.py:435-444 compares softmax scores).
     'l1_loss' / 'cxe_loss' exist with soft_labeling=True (FEW_SHOT.SOFT_LABELING) only, as in the reference (loss.py:364-369)."""
     if loss_weighted:
         raise ValueError("FEW_SHOT.LOSS_WEIGHTED is not supported (box_head/loss.py:349-357)")
-    if neg_support:
-        raise ValueError("FEW_SHOT.NEG_SUPPORT is not supported: the second stage runs without negative support")
+    if neg_support and box_cls_loss != "ce_loss":
+        raise ValueError("FEW_SHOT.NEG_SUPPORT is supported with box_cls_loss='ce_loss' only, not %r: the second stage runs the "
+                         "other losses without negative support" % (box_cls_loss,))
     if method != "concat":
         raise ValueError("FEW_SHOT.SECOND_STAGE_METHOD %r is not supported: only 'concat' (not 'rn' or 'matching')" % (method,))
     row = BOX_CLS_MODES.get(box_cls_loss)
@@ -125,6 +130,25 @@ def box_cls_loss_mode(box_cls_loss, loss_weighted=False, neg_support=False, meth
     if row.soft_only and not soft_labeling:
         raise ValueError("box_cls_loss %r is not supported: %s" % (box_cls_loss, _BOX_CLS_REFUSED[box_cls_loss]))
     return str(box_cls_loss)
+
+
+def check_neg_support(neg_support=False, second_stage=True, linear_fusion=False, box_cls_loss="ce_loss", soft_labeling=False,
+                      shots=1, who="the engine"):
+    """-> bool of FEW_SHOT.NEG_SUPPORT.TURN_ON; ValueError, by name, for the combinations that do not exist: without the second
+    stage, with FEW_SHOT.LINEAR_FUSION (the reference has no compress_dim_conv to call there, box_head.py:136), with any loss but
+    'ce_loss', and with more than one shot (box_head.py:129 expands the negative support without a view per image)."""
+    if not neg_support:
+        return False
+    if not second_stage:
+        raise ValueError("neg_support=True (FEW_SHOT.NEG_SUPPORT) needs the second stage: build %s with second_stage=True" % who)
+    if linear_fusion:
+        raise ValueError("neg_support=True (FEW_SHOT.NEG_SUPPORT) does not exist with linear_fusion=True (FEW_SHOT.LINEAR_FUSION; "
+                         "box_head.py:136 calls compress_dim_conv): build %s with linear_fusion=False" % who)
+    box_cls_loss_mode(box_cls_loss, neg_support=True, soft_labeling=soft_labeling)
+    if int(shots) != 1:
+        raise ValueError("neg_support=True (FEW_SHOT.NEG_SUPPORT) works with one shot only (box_head.py:129), not %d: pass one "
+                         "query per image" % int(shots))
+    return True
 
 
 def box_cls_logits(box_cls_loss="ce_loss", soft_labeling=False):

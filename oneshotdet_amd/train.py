@@ -38,6 +38,13 @@ linear_fusion (FEW_SHOT.LINEAR_FUSION, box_head.py:43,61-72,148; second_stage=Tr
 conv over cat(x, query), GroupNorm, LeakyReLU (no compress_dim_conv).  The conv is split at the concatenation into
 `feature_aggreg.0x` (ROI half) and `feature_aggreg.0q` (query half + bias), which state_dict() merges back into the reference's one
 512-channel `feature_aggreg.0.weight`.  False (the default) leaves the plan, the launches and the keys as they are.
+
+neg_support (FEW_SHOT.NEG_SUPPORT.TURN_ON, generalized_rcnn.py:229-299, box_head.py:128-188, box_head/loss.py:435-444; second_stage=True,
+'ce_loss', one shot, no linear_fusion): every step also gets `neg_queries`, one support crop of another category per image, collated to
+the padded shape of `queries`.  They ride the query backbone as B more rows of the query batch (positives first); the first stage sees the
+first B rows only.  The box head scores the same sampled ROIs against them with the same weights and a margin loss is added
+(train_second_stage.py, include/oneshotdet_hip_neg_support.h).  The state_dict has the keys and shapes of the plain 'ce_loss' model.
+`box_suppress_loss` [2] = (loss_cls_suppress, foreground rows) of the last step.  False (the default): every launch as it is.
 """
 import math
 import os
@@ -106,8 +113,11 @@ class TrainEngine(ForwardPass, BackwardPass, SecondStage, Update, State):
                  process_group=None, wgrad_side_stream=True, optimizer="fused", second_stage=False, ordered_wgrad=None,
                  exchange_single_rank=False, grad_wire_dtype=None, siamese_backbone=True, supp_roialign=True,
                  center_sample=True, loc_loss_type="giou", box_cls_loss="ce_loss", soft_labeling=False, soft_labeling_func="linear",
-                 linear_fusion=False):
+                 linear_fusion=False, neg_support=False):
         self.linear_fusion = bool(linear_fusion)
+        # ValueError by name before anything is built: the combinations FEW_SHOT.NEG_SUPPORT does not exist in
+        self.neg_support = spec.check_neg_support(neg_support, second_stage, linear_fusion, box_cls_loss, soft_labeling,
+                                                  who="the TrainEngine")
         self.center_sample, self.loc_loss_type = spec.loss_mode(center_sample, loc_loss_type)     # ValueError before anything is built
         self.soft_labeling, self.soft_labeling_func = spec.soft_labeling_mode(soft_labeling, soft_labeling_func)
         self.box_cls_loss = spec.box_cls_loss_mode(box_cls_loss, soft_labeling=self.soft_labeling)
@@ -128,6 +138,7 @@ class TrainEngine(ForwardPass, BackwardPass, SecondStage, Update, State):
         self._keep = []
         self.second_stage = bool(second_stage)
         self.box_keys, self.box_losses = None, None       # sampler keys for the next step (None: torch.rand), last losses
+        self.box_suppress_loss = None                     # neg_support: (loss_cls_suppress, foreground rows) of the last step
         from .model import ProposalDepth
         self._prop_depth = None if os.environ.get("OSD_NO_PROP_HINT") else ProposalDepth()
         # A/B switches (measured on one box, tools/ab_round4.sh): both backbones per launch / both towers per launch
@@ -426,9 +437,42 @@ class TrainEngine(ForwardPass, BackwardPass, SecondStage, Update, State):
         self.close()
 
     # ------------------------------------------------------------------------------------------------ step
-    def forward_backward(self, images, queries, gt_boxes, gt_count, with_proposals=True, image_sizes=None):
+    def _neg_query_batch(self, images, queries, neg_queries):
+        """FEW_SHOT.NEG_SUPPORT: validate the negative supports against the queries and stack them behind the queries, as B more rows
+        of the query backbone's batch -> (stacked batch, the negative supports' true sizes or None).  ValueError by name for a
+        missing / unexpected neg_queries, more than one shot, or another padded shape (the reference pads each list to its own
+        maximum, generalized_rcnn.py:228-230: the two agree exactly when the padded shapes are equal)."""
+        from .layers import ImageList
+        if not self.neg_support:
+            if neg_queries is not None:
+                raise ValueError("neg_queries was passed but the engine was built with neg_support=False (FEW_SHOT.NEG_SUPPORT): "
+                                 "build it with neg_support=True or pass neg_queries=None")
+            return queries, None
+        if neg_queries is None:
+            raise ValueError("neg_support=True (FEW_SHOT.NEG_SUPPORT): pass neg_queries=, one support crop of another category per "
+                             "image, collated like queries")
+        neg_sizes = None
+        if isinstance(neg_queries, ImageList):
+            neg_queries, neg_sizes = neg_queries.tensors, neg_queries.image_sizes
+        elif isinstance(neg_queries, ops.PackedImages):
+            neg_sizes = neg_queries.image_sizes
+        if queries.shape[0] != images.shape[0]:
+            raise ValueError("neg_support=True (FEW_SHOT.NEG_SUPPORT) works with one shot only (box_head.py:129): %d queries for %d "
+                             "images; pass one query per image" % (queries.shape[0], images.shape[0]))
+        packed = isinstance(queries, ops.PackedImages)
+        if packed != isinstance(neg_queries, ops.PackedImages) or tuple(neg_queries.shape) != tuple(queries.shape) or \
+                (packed and neg_queries.tensor.shape != queries.tensor.shape):
+            raise ValueError("neg_support=True (FEW_SHOT.NEG_SUPPORT): neg_queries has the padded shape %s, queries %s; collate both "
+                             "to one shape (the same collator call, the same type)" % (tuple(neg_queries.shape), tuple(queries.shape)))
+        if packed:
+            return ops.PackedImages(torch.cat([queries.tensor, neg_queries.tensor]), queries.hw,
+                                    list(queries.image_sizes) + list(neg_queries.image_sizes)), neg_sizes
+        return torch.cat([queries, neg_queries]), neg_sizes
+
+    def forward_backward(self, images, queries, gt_boxes, gt_count, with_proposals=True, image_sizes=None, neg_queries=None):
         """One training forward + backward.  images [B,3,H,W], queries [B*S,3,h,w] fp32 NCHW on the device;
-        gt_boxes [B, G, 4] fp32 xyxy, gt_count [B] int32.  Returns losses [4] = (cls, reg, centerness, num_pos)."""
+        gt_boxes [B, G, 4] fp32 xyxy, gt_count [B] int32.  Returns losses [4] = (cls, reg, centerness, num_pos).
+        neg_queries (neg_support=True only, then required): the negative supports, of the type and padded shape of `queries`."""
         from . import model
         from .layers import ImageList
         # padded batches as the collator hands them over (layers.ImageList, or transforms.collate(..., stem_dtype) =
@@ -442,6 +486,8 @@ class TrainEngine(ForwardPass, BackwardPass, SecondStage, Update, State):
             queries, query_sizes = queries.tensors, queries.image_sizes
         elif isinstance(queries, ops.PackedImages):
             query_sizes = queries.image_sizes
+        # neg_support: the query backbone's batch is (queries, negative supports); everything else reads `queries`
+        qin, neg_sizes = self._neg_query_batch(images, queries, neg_queries)
         main, s1 = streams.current(), self.s1
         # train_step(defer_join) left the previous step's tail (last weight gradients, exchange, update, repack, proposals)
         # running on the side streams: the frozen prefix of this forward goes first, then the main stream joins them
@@ -463,6 +509,9 @@ class TrainEngine(ForwardPass, BackwardPass, SecondStage, Update, State):
         batch = images.shape[0]
         shots = queries.shape[0] // batch
         q_sizes = [tuple(queries.shape[-2:])] * queries.shape[0] if query_sizes is None else [tuple(v) for v in query_sizes]
+        nq_sizes = None
+        if self.neg_support:
+            nq_sizes = [tuple(queries.shape[-2:])] * batch if neg_sizes is None else [tuple(v) for v in neg_sizes]
         rois = model.whole_image_rois(q_sizes, self.device) if self.supp_roialign else None
         # ---- forward: both backbones in lockstep (one launch per layer), query pooling, correlation, head
         lock = self.lockstep
@@ -480,7 +529,8 @@ class TrainEngine(ForwardPass, BackwardPass, SecondStage, Update, State):
                 out.append(ops.shot_mean(v.view(v.shape[0], -1), batch))
             return out
         if lock:
-            (feats, qfeats), (tctx, qctx) = self.backbones_forward(images, queries, after_frozen=af)
+            (feats, qfeats), (tctx, qctx) = self.backbones_forward(images, qin, after_frozen=af)
+            qfeats, nqfeats, qfeats_all = self._split_neg_rows(qfeats, batch)
             pooled = pool(qfeats)
         else:       # the query backbone + pooling on the second stream beside the target backbone
             if deferred is not None and s1 is not None:
@@ -491,7 +541,8 @@ class TrainEngine(ForwardPass, BackwardPass, SecondStage, Update, State):
                 af()
                 af = None
             with streams.on(side):
-                (qfeats,), (qctx,) = self._backbones_forward(self.BBS[1:], (queries,))
+                (qfeats,), (qctx,) = self._backbones_forward(self.BBS[1:], (qin,))
+                qfeats, nqfeats, qfeats_all = self._split_neg_rows(qfeats, batch)
                 pooled = pool(qfeats)
             (feats,), (tctx,) = self._backbones_forward(self.BBS[:1], (images,), af)
             main.wait_stream(side)
@@ -510,8 +561,9 @@ class TrainEngine(ForwardPass, BackwardPass, SecondStage, Update, State):
                 # add_gt_proposals (fcos/inference.py:139-160,279): the ground-truth boxes join the training proposals
                 self.proposals = ops.append_gt_boxes(pb, ps_, pc, gt_boxes, gt_count)
                 if self.second_stage:       # roi_heads on the plain target / query features (generalized_rcnn.py:317), beside
+                    neg_kw = dict(neg_qfeats=nqfeats, neg_q_sizes=nq_sizes) if self.neg_support else {}
                     box_out = self.box_head_forward_backward(feats, qfeats, q_sizes, shots, self.proposals, gt_boxes, gt_count,
-                                                             keys=self.box_keys)    # the first stage's loss and backward
+                                                             keys=self.box_keys, **neg_kw)   # beside the first stage's loss and backward
                     self._bucket_ready("box_head", 0, [ps])
         # ---- loss + backward
         losses, pred_grads = self.loss_and_grads(head_out, gt_boxes, gt_count)
@@ -531,7 +583,11 @@ class TrainEngine(ForwardPass, BackwardPass, SecondStage, Update, State):
         if second:
             if ps is not main:
                 main.wait_stream(ps)
-            self.box_losses, gx, gqs = box_out
+            if self.neg_support:
+                box5, gx, gqs, gqs_neg = box_out
+                self.box_losses, self.box_suppress_loss = box5[:3], box5[3:]
+            else:
+                self.box_losses, gx, gqs = box_out
         with streams.on(side):      # the query branch's small pooling-backward chain beside d feat
             dQ = []
             if not self.supp_roialign:      # the average's gradient: every pixel of a map gets dq / (h * w) / shots, one launch
@@ -552,12 +608,22 @@ class TrainEngine(ForwardPass, BackwardPass, SecondStage, Update, State):
                         full[::shots] = gq
                         gq = full
                     dQ[lvl] = ops.add_mask(dQ[lvl], ops.cast_f32(gq, self.dtype))
+            if self.neg_support:
+                # the query backbone ran on 2B rows: the negative rows' gradient is zero but for the second stage's, at its level
+                full = [torch.zeros(tuple(qa.shape), device=self.device, dtype=self.dtype) for qa in qfeats_all]
+                for l, d in enumerate(dQ):
+                    ops.add_mask(d, None, None, out=full[l][:batch])
+                if second:
+                    for lvl, gq in gqs_neg:
+                        ops.add_mask(ops.cast_f32(gq, self.dtype), None, None, out=full[lvl][batch:])
+                self._keep.append((dQ, qfeats_all))
+                dQ = full
             if not lock:
                 self.backbones_backward([qctx], [dQ], which0=1)
         dP = ops.correlate_levels(d_comb, pooled) if self.corr_levels else [ops.correlate(g, q) for g, q in zip(d_comb, pooled)]
         if second:                      # ... and w.r.t. the target FPN outputs (generalized_rcnn.py:317: the plain features)
             dP = [ops.add_mask(d, ops.cast_f32(g, self.dtype)) for d, g in zip(dP, gx)]
-            self._keep.append((gx, gqs))
+            self._keep.append((gx, gqs, gqs_neg if self.neg_support else None))
         if lock:
             if s1 is not None:
                 main.wait_stream(s1)
@@ -573,7 +639,7 @@ class TrainEngine(ForwardPass, BackwardPass, SecondStage, Update, State):
                     ev = torch.cuda.Event()
                     ev.record(st)
                     events.append(ev)
-            self._deferred = dict(events=events, refs=(qctx, tctx, hctx, feats, qfeats, pooled, combined, head_out, dQ, rois))
+            self._deferred = dict(events=events, refs=(qctx, tctx, hctx, feats, qfeats, qfeats_all, pooled, combined, head_out, dQ, rois))
             return losses
         if s1 is not None:
             main.wait_stream(s1)
@@ -584,6 +650,13 @@ class TrainEngine(ForwardPass, BackwardPass, SecondStage, Update, State):
         if with_proposals and self.pstream is not None:
             main.wait_stream(self.pstream)
         return losses
+
+    def _split_neg_rows(self, qfeats, batch):
+        """neg_support: the query backbone's maps hold the queries' rows, then the negative supports' (leading-dimension slices of
+        an NHWC map: contiguous) -> (queries' maps, negative supports' maps or None, all rows)."""
+        if not self.neg_support:
+            return qfeats, None, qfeats
+        return [f[:batch] for f in qfeats], [f[batch:] for f in qfeats], qfeats
 
     def join(self):
         """Order the current stream after everything a deferred train_step left on the side streams (weight gradients,
@@ -600,7 +673,7 @@ class TrainEngine(ForwardPass, BackwardPass, SecondStage, Update, State):
         they became final during backward (dist_utils.GradExchange); this waits for them."""
         self.exchange.finish()        # buckets not announced during backward (graph replay, single stream) go now
 
-    def train_step(self, images, queries, gt_boxes, gt_count):
+    def train_step(self, images, queries, gt_boxes, gt_count, neg_queries=None):
         """forward + loss + backward + gradient averaging + SGD + repack.  With the fused optimiser each bucket's exchange,
         update and repack run on a side stream as soon as the bucket is final, beside the rest of the backward pass."""
         self._fuse_update = self.opt is None and self._overlap
@@ -609,7 +682,7 @@ class TrainEngine(ForwardPass, BackwardPass, SecondStage, Update, State):
         # already sits on the update / communication stream in fused mode, so nothing is left to enqueue here
         self._defer_now = bool(self.defer_join and self._fuse_update and self.wstream is not None)
         try:
-            losses = self.forward_backward(images, queries, gt_boxes, gt_count)
+            losses = self.forward_backward(images, queries, gt_boxes, gt_count, neg_queries=neg_queries)
         finally:
             self._fuse_update = False
             deferred_step, self._defer_now = self._defer_now, False
@@ -626,6 +699,9 @@ class TrainEngine(ForwardPass, BackwardPass, SecondStage, Update, State):
         """Capture the training step into hipGraphs (forward+loss+backward as one graph, SGD + repack as another, with the
         RCCL all-reduce between them launched normally): ~1500 launches per step become two graph launches.  The learning
         rate is baked in at capture time; call capture() again after changing it."""
+        if self.neg_support:
+            raise ValueError("capture() does not take the negative supports of neg_support=True (FEW_SHOT.NEG_SUPPORT) yet: run "
+                             "train_step(..., neg_queries=) eagerly")
         # static copies of the inputs; a padded batch (layers.ImageList / ops.PackedImages) keeps its per-image sizes, which
         # are baked into the captured graph together with the batch shape
         self._static = [_static_clone(t) for t in (images, queries, gt_boxes, gt_count)]

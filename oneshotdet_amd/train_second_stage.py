@@ -9,7 +9,7 @@ from .ops import ACT_RELU
 
 class SecondStage(object):
     def box_head_forward_backward(self, feats, qfeats, q_sizes, shots, proposals, gt_boxes, gt_count, keys=None,
-                                  want_debug=False):
+                                  want_debug=False, neg_qfeats=None, neg_q_sizes=None):
         """ROIBoxHead in training (box_head.py:100-203) on the training proposals (ground truth appended): subsample on the
         device, box head forward on the 128 sampled ROIs per image with the FIRST query of every image (the reference returns
         the losses from inside its loop over shots), cross-entropy (or, by self.box_cls_loss, the sigmoid focal / mse loss over the one
@@ -17,7 +17,12 @@ class SecondStage(object):
         backward on the current stream: weight / bias / GroupNorm gradients into the flat buffer, the gradient w.r.t. the
         target FPN features as fp32 level maps and w.r.t. the query features' level.
         proposals = (boxes [N,P,4], scores, counts).  keys [N,P]: uniform randoms of the sampler (default: torch.rand).
-        -> (losses [3] = (loss_classifier, loss_box_reg, sampled rows), gx: 5 fp32 maps, (query level, fp32 map [N,h,w,C]))"""
+        -> (losses [3] = (loss_classifier, loss_box_reg, sampled rows), gx: 5 fp32 maps, (query level, fp32 map [N,h,w,C]))
+        neg_qfeats / neg_q_sizes (FEW_SHOT.NEG_SUPPORT, box_head.py:128-139,156-161,180-188; one shot, 'ce_loss'): the feature maps and
+        true sizes of one negative support per image.  The same sampled ROIs are scored against it with the same weights: the ROI half
+        of compress_dim_conv.0 runs once, the first GroupNorm once per addend, and from its output on the trunk runs on one stacked
+        batch of 2M rows, the positive branch's rows first.  losses is then [5] = (loss_classifier, loss_box_reg, sampled rows,
+        loss_cls_suppress, foreground rows) and a fourth value is returned: the negative query's gradient, as the third is the query's."""
         from . import box_head as bh
         from . import model
         b, cv, dt = "roi_heads.box.", self.convs, self.dtype
@@ -40,6 +45,11 @@ class SecondStage(object):
         M = n * S
         slope, gr, eps = spec.BOX_LEAKY_SLOPE, spec.GN_GROUPS, spec.GN_EPS
         linear = getattr(self, "linear_fusion", False)
+        neg = neg_qfeats is not None
+        if neg != bool(getattr(self, "neg_support", False)):
+            raise ValueError("neg_qfeats (FEW_SHOT.NEG_SUPPORT) is passed exactly when the engine was built with neg_support=True")
+        if neg and (shots != 1 or linear or self.box_cls_loss != "ce_loss"):
+            spec.check_neg_support(True, True, linear, self.box_cls_loss, getattr(self, "soft_labeling", False), shots)
         (g2, dg2), (b2, db2) = self.extra[b + "feature_aggreg.1.weight"], self.extra[b + "feature_aggreg.1.bias"]
         if linear:
             # FEW_SHOT.LINEAR_FUSION (box_head.py:61-72,148): the split 3x3 conv takes the place of the split 1x1 conv, its
@@ -61,7 +71,17 @@ class SecondStage(object):
         qh = ops.conv2d(q, c0q.pc, pad=pad0)                                                     # W_q q + b
         x = ops.roi_pool_levels(feats, spec.POOLER_SCALES, sb, sc, spec.BOX_POOL, spec.POOLER_SAMPLING_RATIO)
         u0 = ops.conv2d(x, c0x.pc, pad=pad0)
-        t0 = ops.groupnorm_act_rois(u0, g0, b0, gr, eps, slope, addend=qh, rois_per_add=S, add_stride=1, add_offset=0)
+        q_neg = qh_neg = None
+        R = 2 * M if neg else M                              # rows of the trunk behind the first GroupNorm
+        if neg:
+            nqs = [tuple(s) for s in neg_q_sizes]
+            q_neg = bh.run_query_roi(neg_qfeats, nqs[0] if len(set(nqs)) == 1 else nqs, dt)
+            qh_neg = ops.conv2d(q_neg, c0q.pc, pad=pad0)
+            t0 = torch.empty((R,) + tuple(u0.shape[1:]), device=u0.device, dtype=u0.dtype)
+            for half, add in ((t0[:M], qh), (t0[M:], qh_neg)):
+                ops.groupnorm_act_rois(u0, g0, b0, gr, eps, slope, addend=add, rois_per_add=S, add_stride=1, add_offset=0, out=half)
+        else:
+            t0 = ops.groupnorm_act_rois(u0, g0, b0, gr, eps, slope, addend=qh, rois_per_add=S, add_stride=1, add_offset=0)
         u1 = t1 = u2 = d_u2 = d_t1 = d_u1 = None
         if linear:
             t2 = t0
@@ -70,12 +90,17 @@ class SecondStage(object):
             t1 = ops.groupnorm_act_rois(u1, g1, b1, gr, eps, slope)
             u2 = ops.conv2d(t1, ca.pc, pad=1)
             t2 = ops.groupnorm_act_rois(u2, g2, b2, gr, eps, slope)
-        t2f = t2.view(M, 1, 1, -1)
+        t2f = t2.view(R, 1, 1, -1)
         f6 = ops.conv2d(t2f, fc6.pc, act=ACT_RELU)
         f7 = ops.conv2d(f6, fc7.pc, act=ACT_RELU)
         pred = ops.conv2d(f7, cp.pc)
-        losses, d_pred = ops.box_loss(pred, sl, st, sc, n, S, spec.BOX_LOSS_WEIGHTS[0], spec.BOX_LOSS_WEIGHTS[1],
-                                      grad_stride=cp.pd.cin_k, cls_loss=self.box_cls_loss, soft=ss)
+        if neg:
+            d_pred = torch.empty((R, cp.pd.cin_k), device=pred.device, dtype=pred.dtype)     # d_pred stacked over d_pred_neg
+            losses, _, _ = ops.box_loss_neg_support(pred[:M], pred[M:], sl, st, sc, n, S, spec.BOX_LOSS_WEIGHTS[0],
+                                                    spec.BOX_LOSS_WEIGHTS[1], grad_stride=cp.pd.cin_k, d_out=d_pred)
+        else:
+            losses, d_pred = ops.box_loss(pred, sl, st, sc, n, S, spec.BOX_LOSS_WEIGHTS[0], spec.BOX_LOSS_WEIGHTS[1],
+                                          grad_stride=cp.pd.cin_k, cls_loss=self.box_cls_loss, soft=ss)
         # ---- backward (inline on this stream: M = 1024 ROIs)
 
         def wg(c, xin, dy, pad=0):
@@ -83,7 +108,7 @@ class SecondStage(object):
 
         def dg(c, dy, mask=None):
             return ops.conv2d(dy, c.pd, pad=c.r - 1 - (c.r // 2), mask=mask)
-        d_pred = d_pred.view(M, 1, 1, -1)
+        d_pred = d_pred.view(R, 1, 1, -1)
         wg(cp, f7, d_pred)
         d_f7 = dg(cp, d_pred, mask=f7)
         wg(fc7, f6, d_f7)
@@ -99,28 +124,49 @@ class SecondStage(object):
             d_u1 = ops.groupnorm_act_rois_bwd(u1, g1, b1, d_t1, dg1, db1, gr, eps, slope)
             wg(c3, t0, d_u1)
             d_t0 = dg(c3, d_u1)
-        d_u0 = ops.groupnorm_act_rois_bwd(u0, g0, b0, d_t0, dg0, db0, gr, eps, slope, addend=qh, rois_per_add=S, add_stride=1,
-                                          add_offset=0)
+        d_u0_pos = d_u0_neg = d_qh_neg = d_q_neg = None
+        if neg:
+            # the same u0 under two addends: each half's gradient w.r.t. u0 (dgamma / dbeta accumulate over both calls), their sum
+            # into the ROI half of the conv, each half's ROI sum into the query half (the weight gradient accumulates too)
+            d_u0_pos = ops.groupnorm_act_rois_bwd(u0, g0, b0, d_t0[:M], dg0, db0, gr, eps, slope, addend=qh, rois_per_add=S,
+                                                  add_stride=1, add_offset=0)
+            d_u0_neg = ops.groupnorm_act_rois_bwd(u0, g0, b0, d_t0[M:], dg0, db0, gr, eps, slope, addend=qh_neg, rois_per_add=S,
+                                                  add_stride=1, add_offset=0)
+            d_u0 = ops.add_mask(d_u0_pos, d_u0_neg)
+        else:
+            d_u0 = ops.groupnorm_act_rois_bwd(u0, g0, b0, d_t0, dg0, db0, gr, eps, slope, addend=qh, rois_per_add=S, add_stride=1,
+                                              add_offset=0)
         wg(c0x, x, d_u0, pad=pad0)
         d_x = dg(c0x, d_u0)
-        d_qh = ops.rois_sum(d_u0, n, S)                     # the query half was added to every ROI of its image
+        d_qh = ops.rois_sum(d_u0_pos if neg else d_u0, n, S)   # the query half was added to every ROI of its image
         wg(c0q, q, d_qh, pad=pad0)
         d_q = dg(c0q, d_qh)
+        if neg:
+            d_qh_neg = ops.rois_sum(d_u0_neg, n, S)
+            wg(c0q, q_neg, d_qh_neg, pad=pad0)
+            d_q_neg = dg(c0q, d_qh_neg)
         gx = ops.roi_pool_levels_bwd([(f.shape[1], f.shape[2]) for f in feats], spec.POOLER_SCALES, sb, sc, d_x, spec.BOX_POOL,
                                      spec.POOLER_SAMPLING_RATIO)
-        if uniform:
-            lvl = bh.query_level(*qs1[0])
-            rois = model.whole_image_rois(qs1, self.device)
-            gq = ops.roi_align_bwd(d_q.float(), rois, qf1[lvl].shape, spec.POOLER_SCALES[lvl], spec.BOX_POOL, spec.BOX_POOL,
-                                   spec.POOLER_SAMPLING_RATIO)
-            gqs = [(lvl, gq)]
-        else:                                                # padded query batch: every whole-image box picks its own level
-            boxes = model.whole_image_rois(qs1, self.device)[:, 1:].reshape(n, 1, 4).contiguous()
-            maps = ops.roi_pool_levels_bwd([(f.shape[1], f.shape[2]) for f in qf1], spec.POOLER_SCALES, boxes, None, d_q,
+
+        def query_grad(d_q, qf, qs):
+            if len(set(qs)) == 1:
+                lvl = bh.query_level(*qs[0])
+                rois = model.whole_image_rois(qs, self.device)
+                gq = ops.roi_align_bwd(d_q.float(), rois, qf[lvl].shape, spec.POOLER_SCALES[lvl], spec.BOX_POOL, spec.BOX_POOL,
+                                       spec.POOLER_SAMPLING_RATIO)
+                return [(lvl, gq)]
+            # padded query batch: every whole-image box picks its own level
+            boxes = model.whole_image_rois(qs, self.device)[:, 1:].reshape(n, 1, 4).contiguous()
+            maps = ops.roi_pool_levels_bwd([(f.shape[1], f.shape[2]) for f in qf], spec.POOLER_SCALES, boxes, None, d_q,
                                            spec.BOX_POOL, spec.POOLER_SAMPLING_RATIO)
-            gqs = list(enumerate(maps))
+            return list(enumerate(maps))
+        gqs = query_grad(d_q, qf1, qs1)
+        gqs_neg = query_grad(d_q_neg, neg_qfeats, nqs) if neg else None
         self._keep.append((sb, sl, st, si, sc, q, qh, x, u0, t0, u1, t1, u2, t2, f6, f7, pred, d_pred, d_f7, d_f6, d_t2, d_u2,
-                           d_t1, d_u1, d_t0, d_u0, d_x, d_qh, d_q, keys, ss))
+                           d_t1, d_u1, d_t0, d_u0, d_x, d_qh, d_q, keys, ss, q_neg, qh_neg, d_u0_pos, d_u0_neg, d_qh_neg, d_q_neg,
+                           neg_qfeats))
         if want_debug:
-            self.last_box = dict(boxes=sb, labels=sl, targets=st, index=si, counts=sc, pred=pred, soft=ss)
-        return losses, gx, gqs
+            self.last_box = dict(boxes=sb, labels=sl, targets=st, index=si, counts=sc, pred=pred[:M] if neg else pred, soft=ss)
+            if neg:
+                self.last_box["pred_neg"] = pred[M:]
+        return (losses, gx, gqs, gqs_neg) if neg else (losses, gx, gqs)

@@ -1,0 +1,98 @@
+"""CPU: include/oneshotdet_hip_neg_support.h under the rules tests/test_abi.py, tests/test_abi_coverage.py, tests/test_abi_box_modes.py and
+tests/test_abi_soft_labels.py hold the other three headers to — the function it declares is exactly the one the binding's fourth table
+(_lib.SIGNATURES_NEG_SUPPORT) lists and the library exports, and it names a GPU test that exists and calls it."""
+import ctypes
+import os
+import re
+
+import pytest
+
+TESTS = os.path.dirname(os.path.abspath(__file__))
+ROOT = os.path.dirname(TESTS)
+GPU = "test_gpu_box_neg_support.py"
+HEADER = "oneshotdet_hip_neg_support.h"
+OTHER_HEADERS = ("oneshotdet_hip.h", "oneshotdet_hip_box_modes.h", "oneshotdet_hip_soft_labels.h")
+
+# function -> the test of GPU that calls it by name through _lib.call and checks what it computed
+COVERED = {
+    "osd_box_loss_neg_support": "test_c_entry_with_padded_strides_null_gradients_bad_labels_and_error_codes",
+}
+# the `ops` wrapper that reaches the function -> a test that calls it against the reference fixture
+THROUGH_OPS = {
+    "osd_box_loss_neg_support": ("box_loss_neg_support", "grad_stride=", "test_loss_kernel_matches_the_reference_fixture"),
+}
+
+
+def declared(header):
+    """the regex of tests/test_abi.py"""
+    src = open(os.path.join(ROOT, "include", header)).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    return sorted(set(re.findall(r"\b(osd_[a-z0-9_]+)\s*\(", src)))
+
+
+@pytest.fixture(scope="module")
+def lib_path():
+    from oneshotdet_amd import build
+    return build.build_library(verbose=False)
+
+
+def test_header_and_fourth_binding_table_agree():
+    from oneshotdet_amd import _lib
+    names = declared(HEADER)
+    assert names == sorted(_lib.SIGNATURES_NEG_SUPPORT.keys()) == ["osd_box_loss_neg_support"]
+    # the four tables are disjoint, and the new header adds nothing to the other three's inventories
+    others = set(_lib.SIGNATURES) | set(_lib.SIGNATURES_BOX_MODES) | set(_lib.SIGNATURES_SOFT_LABELS)
+    for h in OTHER_HEADERS:
+        others |= set(declared(h))
+    assert not set(names) & others
+    assert declared("oneshotdet_hip_box_modes.h") == ["osd_box_decode_opt", "osd_box_loss_opt"]
+    assert declared("oneshotdet_hip_soft_labels.h") == ["osd_box_loss_soft", "osd_box_match_sample_soft"]
+    # osd_box_loss's arguments + (pred_neg, margin, w_suppress, d_pred_neg)
+    new, old = _lib.SIGNATURES_NEG_SUPPORT["osd_box_loss_neg_support"], _lib.SIGNATURES["osd_box_loss"]
+    assert new[0] is old[0] and len(new[1]) == len(old[1]) + 4
+    assert sorted(map(str, new[1])) == sorted(map(str, old[1] + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_float, ctypes.c_float]))
+    # the prototype has as many parameters as the table
+    src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", HEADER)).read(), flags=re.S)
+    for name, (_, args) in _lib.SIGNATURES_NEG_SUPPORT.items():
+        params = re.search(r"\b%s\s*\((.*?)\)\s*;" % name, src, flags=re.S).group(1)
+        assert len(params.split(",")) == len(args), name
+        for word in ("pred_neg", "d_pred_neg", "margin", "w_suppress"):
+            assert re.search(r"\b%s\b" % word, params), word
+    # the build depends on the header, and the ABI version is not part of this change
+    from oneshotdet_amd import build
+    assert HEADER in open(build.__file__).read()
+    assert _lib.ABI_VERSION == 4
+    # the header states the kernel's answer where the reference has none
+    text = open(os.path.join(ROOT, "include", HEADER)).read()
+    assert "K == 0" in text and "NaN" in text
+
+
+def test_library_exports_and_binds_the_new_entry(lib_path):
+    import torch  # noqa: F401  resolves libamdhip64.so.7 to the runtime torch ships
+    raw = ctypes.CDLL(lib_path)
+    for name in declared(HEADER):
+        assert hasattr(raw, name), name
+    from oneshotdet_amd import _lib
+    lib = _lib.load()
+    for name, (res, args) in _lib.SIGNATURES_NEG_SUPPORT.items():
+        fn = getattr(lib, name)
+        assert fn.restype is res and list(fn.argtypes) == list(args), name
+    assert lib.osd_abi_version() == _lib.ABI_VERSION == 4
+
+
+def test_the_new_entry_names_a_gpu_test_that_calls_it():
+    assert sorted(COVERED) == sorted(THROUGH_OPS) == declared(HEADER)
+    src = open(os.path.join(TESTS, GPU)).read()
+    assert "pytestmark = pytest.mark.gpu" in src
+    ops_src = open(os.path.join(ROOT, "oneshotdet_amd", "ops.py")).read()
+
+    def body(test):
+        m = re.search(r"^def %s\(.*?(?=^def |^@pytest|\Z)" % re.escape(test), src, flags=re.S | re.M)
+        assert m, test
+        return m.group(0)
+    for fn, test in COVERED.items():
+        assert '"%s"' % fn in body(test), (fn, test)                    # called by name through _lib.call
+    for fn, (wrapper, kw, test) in THROUGH_OPS.items():
+        assert "ops.%s(" % wrapper in body(test) and kw in body(test), (fn, test)
+        wbody = re.search(r"^def %s\(.*?(?=^def |\Z)" % wrapper, ops_src, flags=re.S | re.M).group(0)
+        assert '"%s"' % fn in wbody, (fn, wrapper)
