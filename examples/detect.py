@@ -49,13 +49,14 @@ def main():
     roialign = not args.no_supp_roialign
     if args.checkpoint:
         siamese = checkpoint.has_query_backbone(args.checkpoint)       # the file's own mode
-    shapes = spec.hot_path_shapes(siamese) if args.first_stage_only else spec.full_model_shapes(
-        siamese, box_cls_loss=args.box_cls_loss, soft_labeling=args.soft_labeling, linear_fusion=args.linear_fusion)
+    # the model's options (spec.MODEL_OPTIONS), once: the detector's, and those among them that decide the state_dict's shapes
+    options = dict(siamese_backbone=siamese, supp_roialign=roialign, box_cls_loss=args.box_cls_loss, soft_labeling=args.soft_labeling,
+                   linear_fusion=args.linear_fusion, neg_support=args.neg_support)
+    shape_options = {name: options[name] for name in spec.SHAPE_OPTIONS}
+    shapes = spec.hot_path_shapes(siamese) if args.first_stage_only else spec.full_model_shapes(**shape_options)
     defaults = {k: torch.from_numpy(v) for k, v in synth.make_state_dict(shapes).items()}
     if args.checkpoint:
-        sd, extras = checkpoint.load_checkpoint(args.checkpoint, defaults=defaults, siamese_backbone=siamese,
-                                                box_cls_loss=args.box_cls_loss, soft_labeling=args.soft_labeling,
-                                                linear_fusion=args.linear_fusion)
+        sd, extras = checkpoint.load_checkpoint(args.checkpoint, defaults=defaults, **shape_options)
         print("loaded", args.checkpoint, "(%s backbone)" % ("siamese" if siamese else "shared"),
               {k: v for k, v in extras.items() if not isinstance(v, dict)})
         if "box_cls_loss" in extras and str(extras["box_cls_loss"]) != args.box_cls_loss and not args.first_stage_only:
@@ -65,16 +66,14 @@ def main():
             raise SystemExit("%s was trained with supp_roialign=%r: %s --no-supp-roialign" % (
                 args.checkpoint, bool(extras["supp_roialign"]), "drop" if roialign is False else "add"))
     elif args.c2:
-        sd = checkpoint.load_c2_resnet(args.c2, defaults, siamese_backbone=siamese, box_cls_loss=args.box_cls_loss,
-                                       soft_labeling=args.soft_labeling, linear_fusion=args.linear_fusion)
+        sd = checkpoint.load_c2_resnet(args.c2, defaults, **shape_options)
         print("backbones initialised from", args.c2)
     else:
         sd = defaults
         print("synthetic weights (no checkpoint given)")
-    det = modules.OneShotDetector(sd, dtype=torch.bfloat16 if args.dtype == "bf16" else torch.float32, siamese_backbone=siamese,
-                                  supp_roialign=roialign, box_cls_loss=args.box_cls_loss, soft_labeling=args.soft_labeling,
-                                  linear_fusion=args.linear_fusion and not args.first_stage_only,
-                                  neg_support=args.neg_support and not args.first_stage_only)
+    if args.first_stage_only:
+        options.update(linear_fusion=False, neg_support=False)
+    det = modules.OneShotDetector(sd, dtype=torch.bfloat16 if args.dtype == "bf16" else torch.float32, **options)
     # two targets and two queries of different sizes
     targets = [torch.from_numpy(synth.make_images("ex.t%d" % i, 1, h, w)[0]) for i, (h, w) in enumerate([(480, 640), (512, 384)])]
     queries = [torch.from_numpy(synth.make_images("ex.q%d" % i, 1, h, w)[0]) for i, (h, w) in enumerate([(127, 127), (96, 160)])]

@@ -80,36 +80,28 @@ def main():
                          "rule for choosing the negative support (its dataset's negative category is always -1); this example's own "
                          "rule: sample i's negative support is the support crop of sample (i + 1) mod batch")
     args = ap.parse_args()
-    if not args.first_stage_only:
-        spec.box_cls_loss_mode(args.box_cls_loss, soft_labeling=args.soft_labeling)      # l1_loss / cxe_loss without --soft-labeling: refused here
-    neg_support = spec.check_neg_support(args.neg_support, not args.first_stage_only, args.linear_fusion, args.box_cls_loss,
-                                         args.soft_labeling, who="the example")
-    siamese = not args.shared_backbone
-    roialign = not args.no_supp_roialign
-    center_sample = not args.no_center_sample
+    # the model's options (spec.MODEL_OPTIONS), once: for the engine and, on --resume, as what the checkpoint is expected to hold
+    options = dict(siamese_backbone=not args.shared_backbone, supp_roialign=not args.no_supp_roialign,
+                   center_sample=not args.no_center_sample, loc_loss_type=args.loc_loss_type, box_cls_loss=args.box_cls_loss,
+                   soft_labeling=args.soft_labeling, soft_labeling_func=args.soft_labeling_func,
+                   linear_fusion=args.linear_fusion and not args.first_stage_only, neg_support=args.neg_support)
+    # refused here, by name: l1_loss / cxe_loss without --soft-labeling, --neg-support in a combination it does not exist in
+    spec.check_options("the example", not args.first_stage_only, **options)
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
     dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float32
-    shapes = spec.hot_path_shapes(siamese) if args.first_stage_only else spec.full_model_shapes(
-        siamese, box_cls_loss=args.box_cls_loss, soft_labeling=args.soft_labeling, linear_fusion=args.linear_fusion)
+    shapes = spec.hot_path_shapes(options["siamese_backbone"]) if args.first_stage_only else spec.full_model_shapes(
+        **{name: options[name] for name in spec.SHAPE_OPTIONS})
 
     def make_engine(sd):
-        return train.TrainEngine(sd, dtype=dtype, lr=0.0005, second_stage=not args.first_stage_only, siamese_backbone=siamese,
-                                 supp_roialign=roialign, center_sample=center_sample, loc_loss_type=args.loc_loss_type,
-                                 box_cls_loss=args.box_cls_loss, soft_labeling=args.soft_labeling,
-                                 soft_labeling_func=args.soft_labeling_func,
-                                 linear_fusion=args.linear_fusion and not args.first_stage_only, neg_support=neg_support)
+        return train.TrainEngine(sd, dtype=dtype, lr=0.0005, second_stage=not args.first_stage_only, **options)
     start = 0
     last = os.path.join(args.out, "last_checkpoint")
     if args.resume and os.path.exists(last):
-        eng, start = checkpoint.resume_training(open(last).read().strip(), make_engine, siamese_backbone=siamese,
-                                                supp_roialign=roialign, center_sample=center_sample,
-                                                loc_loss_type=args.loc_loss_type,
-                                                box_cls_loss=None if args.first_stage_only else args.box_cls_loss,
-                                                soft_labeling=None if args.first_stage_only else args.soft_labeling,
-                                                soft_labeling_func=None if args.first_stage_only else args.soft_labeling_func,
-                                                linear_fusion=None if args.first_stage_only else args.linear_fusion,
-                                                neg_support=None if args.first_stage_only else neg_support)
+        # a first-stage-only run says nothing about the second stage's options: whatever the file holds
+        expected = {name: None if args.first_stage_only and spec.MODEL_OPTIONS[name].scope == "second_stage" else value
+                    for name, value in options.items()}
+        eng, start = checkpoint.resume_training(open(last).read().strip(), make_engine, **expected)
         print("resumed at iteration", start)
     else:
         eng = make_engine(synth.make_state_dict(shapes))      # or checkpoint.load_checkpoint / load_c2_resnet, see detect.py
@@ -140,7 +132,7 @@ def main():
         images = T.collate(imgs, spec.SIZE_DIVISIBILITY, stem_dtype=dtype)
         queries = T.collate(supps, spec.SIZE_DIVISIBILITY, stem_dtype=dtype)
         # the same crops rotated by one: the same padded shape as `queries`, which the engine requires
-        neg_queries = T.collate(supps[1:] + supps[:1], spec.SIZE_DIVISIBILITY, stem_dtype=dtype) if neg_support else None
+        neg_queries = T.collate(supps[1:] + supps[:1], spec.SIZE_DIVISIBILITY, stem_dtype=dtype) if args.neg_support else None
         g = max(len(t) for t in targets)
         gt = torch.zeros(args.batch, g, 4)
         for i, t in enumerate(targets):

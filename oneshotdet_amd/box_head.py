@@ -25,12 +25,11 @@ class BoxHeadWeights(object):
 
     def __init__(self, sd, dtype, prefix="roi_heads.box.", box_cls_loss="ce_loss", soft_labeling=False, linear_fusion=False,
                  neg_support=False):
-        # FEW_SHOT.NEG_SUPPORT: validated (ValueError by name) and otherwise nothing: inference discards the negative branch
-        self.neg_support = spec.check_neg_support(neg_support, True, linear_fusion, box_cls_loss, soft_labeling, who="the box head")
-        self.soft_labeling = bool(soft_labeling)
-        self.linear_fusion = spec.check_linear_fusion(sd, linear_fusion, prefix)        # before anything is packed
-        self.box_cls_loss = spec.box_cls_loss_mode(box_cls_loss, soft_labeling=self.soft_labeling)
-        spec.check_box_cls_score(sd, self.box_cls_loss, prefix, soft_labeling=self.soft_labeling)      # a 1-row cls_score must never be read as two logits
+        # spec.MODEL_OPTIONS, and the state_dict's layout and cls_score against them: ValueError by name before anything is packed.
+        # FEW_SHOT.NEG_SUPPORT is validated and otherwise nothing: inference discards the negative branch
+        given = spec.options_in(locals())
+        options = spec.check_options("the box head", True, box_sd=sd, box_prefix=prefix, **given)
+        vars(self).update((name, getattr(options, name)) for name in given)
         c = spec.FPN_OUT
         if self.linear_fusion:
             # FEW_SHOT.LINEAR_FUSION: the 3x3 conv over cat(x, query), split at the concatenation like the 1x1 conv below (zero

@@ -7,21 +7,14 @@ expected key the loaded key that is its LONGEST suffix), so a reference `model_X
 The Caffe2 / Detectron `.pkl` route (utils/c2_model_loading.py:12-175; `MODEL.WEIGHT: catalog://ImageNetPretrained/MSRA/R-50`)
 is `load_c2_resnet`: blob names are translated to the torchvision-style names the reference maps them to, and the same
 suffix alignment then fills BOTH backbones (every `*.body.layer1.0.conv1.weight` ends with `layer1.0.conv1.weight`).
-siamese_backbone (FEW_SHOT.SIAMESE_BACKBONE): True = the two-backbone model (a shared-backbone file fills `supp_backbone.*` from
-`backbone.*` by that suffix match, as the reference does); False = the shared-backbone model, whose key set has no
-`supp_backbone.*` (a two-backbone file's query backbone is ignored, as the reference ignores keys its model does not have).
-supp_roialign (FEW_SHOT.SUPP_ROIALIGN) changes no key: the query pooling has no weights, so loading is the same in both modes;
-training checkpoints record it, and `resume_training` refuses to continue a run in the other mode.  The same holds for the loss
-options center_sample / loc_loss_type (FCOS.CENTER_SAMPLE / FCOS.LOC_LOSS_TYPE): the loss has no parameters.
-box_cls_loss (FEW_SHOT.SECOND_STAGE_CLS_LOSS) changes a SHAPE: `roi_heads.box.predictor.cls_score.*` has 2 rows for 'ce_loss' and
-1 for 'focal_loss' / 'mse_loss'.  Loading checks the shapes of the mode it is given; the two one-row modes share their shapes, so
-training checkpoints record the mode and `resume_training` refuses to continue a run on the other loss.
-soft_labeling / soft_labeling_func (FEW_SHOT.SOFT_LABELING / SOFT_LABELING_FUNC) change no key and no shape by themselves ('l1_loss'
-has 'mse_loss's shapes, 'cxe_loss' has 'ce_loss's): training checkpoints record both, a file without the fields was trained with
-(False, "linear"), and `resume_training` refuses a mismatch.
-linear_fusion (FEW_SHOT.LINEAR_FUSION) changes the KEY SET: with it there is no `roi_heads.box.compress_dim_conv.*` and
-`feature_aggreg.0.weight` has 512 input channels.  Loading a file trained with the other setting raises a ValueError that names the
-option (spec.check_linear_fusion) before any key is looked up; training checkpoints record it, a file without the field means False.
+The model's options (spec.MODEL_OPTIONS): training checkpoints record every one, and `resume_training` refuses to continue a run
+with another value.  The loaders take those that decide a key or a shape (spec.SHAPE_OPTIONS); the others (a pooling, a loss, soft
+labels, a negative support) have no weights.  siamese_backbone: True = the two-backbone model (a shared-backbone file fills
+`supp_backbone.*` from `backbone.*` by that suffix match, as the reference does); False = the shared-backbone model, whose key
+set has no `supp_backbone.*` (a two-backbone file's query backbone is ignored, as the reference ignores keys its model does not
+have).  box_cls_loss (with soft_labeling for 'l1_loss' / 'cxe_loss'): `roi_heads.box.predictor.cls_score.*` has 2 rows or 1; the
+one-row modes share their shapes.  linear_fusion: no `roi_heads.box.compress_dim_conv.*` and a 512-channel `feature_aggreg.0.weight`;
+a file trained with the other setting is refused by name (spec.check_linear_fusion) before any key is looked up.
 """
 import os
 import pickle
@@ -81,19 +74,22 @@ def has_query_backbone(path_or_sd):
     return any(k.startswith("supp_backbone.") for k in strip_prefix_if_present(sd))
 
 
+def _model_shapes(siamese_backbone, box_cls_loss, soft_labeling, linear_fusion):
+    """Which shapes the model of these options (spec.SHAPE_OPTIONS) has -> (the hot path's, the box head's, for a source that has one)."""
+    return spec.hot_path_shapes(siamese_backbone), spec.box_head_shapes(box_cls_loss=box_cls_loss, soft_labeling=soft_labeling,
+                                                                         linear_fusion=linear_fusion)
+
+
 def load_checkpoint(path, second_stage=None, defaults=None, siamese_backbone=True, box_cls_loss="ce_loss", soft_labeling=False,
                     linear_fusion=False):
     """Read a reference `.pth` (or a bare state_dict file) -> (state_dict under the reference's key names, extras).
     second_stage: True = require roi_heads.box.*, False = first stage only, None = take it when present.
     defaults: values for keys the file lacks (utils/checkpoint.py:107-115 keeps the model's own initialisation for
     FEW_SHOT.UNLOAD_KEYWORD modules); without it a missing key is an error.
-    siamese_backbone=False: read the shared-backbone model's keys only (any `supp_backbone.*` in the file is ignored).
-    box_cls_loss: the second stage's classification loss the file was trained with (the shape of its cls_score); 'l1_loss' /
-    'cxe_loss' with soft_labeling=True.  linear_fusion: FEW_SHOT.LINEAR_FUSION of the model that wrote the file."""
+    siamese_backbone, box_cls_loss, soft_labeling, linear_fusion (spec.SHAPE_OPTIONS): of the model that wrote the file, see above."""
     data = _read(path)
     loaded = data.pop("model")
-    shapes = spec.hot_path_shapes(siamese_backbone)
-    box = spec.box_head_shapes(box_cls_loss=box_cls_loss, soft_labeling=soft_labeling, linear_fusion=linear_fusion)
+    shapes, box = _model_shapes(siamese_backbone, box_cls_loss, soft_labeling, linear_fusion)
     probe = strip_prefix_if_present(loaded)
     has_box = any(k.endswith("box.fc6.weight") for k in probe)
     if second_stage or (second_stage is None and has_box):
@@ -134,125 +130,64 @@ def save_checkpoint(path, state_dict, tag_last=True, **extras):
     return path
 
 
+def engine_options(engine):
+    """{name: value} of spec.MODEL_OPTIONS as an engine (or a stand-in for one) carries them: an attribute it lacks means the row's
+    default."""
+    return OrderedDict((name, type(row.default)(getattr(engine, name, row.default))) for name, row in spec.MODEL_OPTIONS.items())
+
+
 def save_training_checkpoint(path, engine, iteration, tag_last=True):
     """utils/checkpoint.py:33-50 as the trainer calls it (engine/trainer.py:111-119): model + optimizer + iteration.
-    `optimizer` holds TrainEngine.optimizer_state_dict() (momentum buffers under reference names, steps taken, lr);
-    `siamese_backbone` the engine's mode (a shared engine writes no `supp_backbone.*`); `supp_roialign` its query pooling (the
-    only record of it: the pooling has no weights); `center_sample` / `loc_loss_type` the FCOS loss it trained with (likewise);
-    `box_cls_loss` the second stage's classification loss (the two one-logit losses have the same shapes); `soft_labeling` /
-    `soft_labeling_func` the soft labels it was held against (no weights either); `linear_fusion` the box head's layout (the key set
-    shows it too); `neg_support` whether it trained with a negative support (FEW_SHOT.NEG_SUPPORT: no weights, no keys)."""
+    `optimizer` holds TrainEngine.optimizer_state_dict() (momentum buffers under reference names, steps taken, lr).  One more field
+    per row of spec.MODEL_OPTIONS: the options the engine trained with, most of which leave no other trace in the file."""
     return save_checkpoint(path, engine.state_dict(), tag_last=tag_last, optimizer=engine.optimizer_state_dict(),
-                           iteration=int(iteration), siamese_backbone=bool(getattr(engine, "siamese_backbone", True)),
-                           supp_roialign=bool(getattr(engine, "supp_roialign", True)),
-                           center_sample=bool(getattr(engine, "center_sample", spec.CENTER_SAMPLE)),
-                           loc_loss_type=str(getattr(engine, "loc_loss_type", spec.LOC_LOSS_TYPE)),
-                           box_cls_loss=str(getattr(engine, "box_cls_loss", spec.BOX_CLS_LOSS)),
-                           soft_labeling=bool(getattr(engine, "soft_labeling", spec.SOFT_LABELING)),
-                           soft_labeling_func=str(getattr(engine, "soft_labeling_func", spec.SOFT_LABELING_FUNC)),
-                           linear_fusion=bool(getattr(engine, "linear_fusion", spec.LINEAR_FUSION)),
-                           neg_support=bool(getattr(engine, "neg_support", spec.NEG_SUPPORT)))
+                           iteration=int(iteration), **engine_options(engine))
 
 
-def _loss_name(mode):
-    return "the %s FCOS loss (center_sample=%r, loc_loss_type=%r)" % (
-        ("centre-sampled " if mode[0] else "whole-box ") + mode[1], mode[0], mode[1])
+def _file_options(data):
+    """{name: value} of spec.MODEL_OPTIONS as a checkpoint's dictionary records them; for a field it lacks (a file written before
+    the option existed) the row's default, or what the group's rule reads from the keys."""
+    sd, out = strip_prefix_if_present(data["model"]), {}
+    for name, row in spec.MODEL_OPTIONS.items():
+        v, absent = data.get(name), spec.OPTION_RULES[row.group].absent
+        if v is None:
+            v = row.default if absent is None else absent(sd)[spec.OPTION_GROUPS[row.group].index(name)]
+        out[name] = type(row.default)(v)
+    return out
+
+
+def _trained_with(path, group, values):
+    return "%s was trained with %s [%s]" % (path, spec.describe_group(group, values),
+                                            " / ".join(spec.MODEL_OPTIONS[n].config for n in spec.OPTION_GROUPS[group]))
 
 
 def resume_training(path, make_engine, siamese_backbone=None, supp_roialign=None, center_sample=None, loc_loss_type=None,
                     box_cls_loss=None, soft_labeling=None, soft_labeling_func=None, linear_fusion=None, neg_support=None):
     """Load a checkpoint written by save_training_checkpoint: make_engine(state_dict) -> TrainEngine; its momentum and
-    step count are restored.  Returns (engine, iteration).  The file's mode (recorded by save_training_checkpoint; for
-    older files: whether it holds `supp_backbone.*`) must be the engine's: a resumed run never ties or unties weights
-    behind the caller's back.  siamese_backbone: the mode the caller expects (None: whatever the file holds).  The same
-    for the query pooling: supp_roialign is the caller's expectation, the file's record (True when it has none, the
-    files written before the option existed) must match it and the engine's.  And for the FCOS loss: center_sample /
-    loc_loss_type are the caller's expectations (None: whatever the file holds), a file without the fields was trained with
-    (True, "giou"), the only loss there was.  And for the second stage's classification loss: box_cls_loss is the caller's
-    expectation (None: whatever the file holds), a file without the field was trained with "ce_loss".  And for the soft labels:
-    soft_labeling / soft_labeling_func are the caller's expectations (None: whatever the file holds), a file without the fields was
-    trained with (False, "linear"); the function only matters where soft labels are on.  And for the box head's layout:
-    linear_fusion is the caller's expectation (None: whatever the file holds), a file without the field was trained with False.
-    And for the negative support: neg_support is the caller's expectation (None: whatever the file holds), a file without the field
-    was trained with False."""
+    step count are restored.  Returns (engine, iteration).  A resumed run never changes an option behind the caller's back.  For
+    every row of spec.MODEL_OPTIONS the file's value is its record (a file written before the option existed: the row's default),
+    and the keyword is what the caller expects (None: whatever the file holds).  An expectation that differs from the file is
+    refused before make_engine is called, an engine that make_engine built otherwise after it: ValueError naming the file, the
+    option and both values.  The table's groups are looked at from the last to the first, each by its spec.OPTION_RULES."""
+    expected = spec.options_in(locals())
     data = _read(path)
-    neg = data.get("neg_support")
-    neg = spec.NEG_SUPPORT if neg is None else bool(neg)
-    if neg_support is not None and bool(neg_support) != neg:
-        raise ValueError("%s was trained with neg_support=%r (FEW_SHOT.NEG_SUPPORT); resuming it with neg_support=%r would continue "
-                         "the run on another objective: build the engine with neg_support=%r" % (path, neg, bool(neg_support), neg))
-    fusion = data.get("linear_fusion")
-    fusion = spec.LINEAR_FUSION if fusion is None else bool(fusion)
-    if linear_fusion is not None and bool(linear_fusion) != fusion:
-        raise ValueError("%s was trained with linear_fusion=%r (FEW_SHOT.LINEAR_FUSION); resuming it with linear_fusion=%r would "
-                         "continue another model: build the engine with linear_fusion=%r"
-                         % (path, fusion, bool(linear_fusion), fusion))
-    soft = (data.get("soft_labeling"), data.get("soft_labeling_func"))
-    soft = spec.soft_labeling_mode(spec.SOFT_LABELING if soft[0] is None else bool(soft[0]),
-                                   spec.SOFT_LABELING_FUNC if soft[1] is None else str(soft[1]))
-    want_soft = spec.soft_labeling_mode(soft[0] if soft_labeling is None else soft_labeling,
-                                        soft[1] if soft_labeling_func is None else soft_labeling_func)
-    if want_soft[0] != soft[0] or (soft[0] and want_soft[1] != soft[1]):
-        raise ValueError("%s was trained with soft_labeling=%r, soft_labeling_func=%r; resuming it with soft_labeling=%r, "
-                         "soft_labeling_func=%r would continue the run on other labels: build the engine with soft_labeling=%r, "
-                         "soft_labeling_func=%r" % (path, soft[0], soft[1], want_soft[0], want_soft[1], soft[0], soft[1]))
-    box = data.get("box_cls_loss")
-    box = spec.BOX_CLS_LOSS if box is None else spec.box_cls_loss_mode(str(box), soft_labeling=soft[0])
-    if box_cls_loss is not None and spec.box_cls_loss_mode(box_cls_loss, soft_labeling=soft[0]) != box:
-        raise ValueError("%s was trained with box_cls_loss=%r; resuming it with box_cls_loss=%r would continue the run on another "
-                         "objective: build the engine with box_cls_loss=%r" % (path, box, box_cls_loss, box))
-    loss = (data.get("center_sample"), data.get("loc_loss_type"))
-    loss = (spec.CENTER_SAMPLE if loss[0] is None else bool(loss[0]), spec.LOC_LOSS_TYPE if loss[1] is None else str(loss[1]))
-    want = spec.loss_mode(loss[0] if center_sample is None else center_sample, loss[1] if loc_loss_type is None else loc_loss_type)
-    if want != loss:
-        raise ValueError("%s was trained with %s; resuming it with %s would continue the run on another objective: build the "
-                         "engine with center_sample=%r, loc_loss_type=%r" % (path, _loss_name(loss), _loss_name(want), loss[0], loss[1]))
-    pool = data.get("supp_roialign")
-    pool = True if pool is None else bool(pool)
-    if supp_roialign is not None and bool(supp_roialign) != pool:
-        raise ValueError("%s was trained with %s; resuming it with %s would continue another model: build the engine with "
-                         "supp_roialign=%r" % (path, _POOL[pool], _POOL[bool(supp_roialign)], pool))
-    mode = data.get("siamese_backbone")
-    mode = has_query_backbone(data["model"]) if mode is None else bool(mode)
-    if siamese_backbone is not None and bool(siamese_backbone) != mode:
-        raise ValueError("%s holds a %s model; resuming it as a %s model would %s the query backbone's weights: load it with "
-                         "load_checkpoint(..., siamese_backbone=%r) into a fresh run instead"
-                         % (path, _MODE[mode], _MODE[bool(siamese_backbone)], "untie" if siamese_backbone else "tie",
-                            bool(siamese_backbone)))
-    sd, extras = load_checkpoint(path, siamese_backbone=mode, box_cls_loss=box, soft_labeling=soft[0], linear_fusion=fusion)
+    record, trained = _file_options(data), OrderedDict()
+    for group in reversed(spec.OPTION_GROUPS):
+        trained[group], want = spec.group_values(group, record), spec.group_values(group, record, expected)
+        if spec.OPTION_RULES[group].differs(trained[group], want):
+            raise ValueError("%s; resuming it with %s would %s: build the engine with %s"
+                             % (_trained_with(path, group, trained[group]), spec.describe_group(group, want),
+                                spec.OPTION_RULES[group].why, spec.describe_group(group, trained[group], words=False)))
+    sd, extras = load_checkpoint(path, **{name: record[name] for name in spec.SHAPE_OPTIONS})
     eng = make_engine(sd)
-    built_neg = bool(getattr(eng, "neg_support", spec.NEG_SUPPORT))
-    if built_neg != neg:
-        raise ValueError("%s was trained with neg_support=%r (FEW_SHOT.NEG_SUPPORT) but make_engine built an engine with "
-                         "neg_support=%r" % (path, neg, built_neg))
-    built_fusion = bool(getattr(eng, "linear_fusion", spec.LINEAR_FUSION))
-    if built_fusion != fusion:
-        raise ValueError("%s was trained with linear_fusion=%r (FEW_SHOT.LINEAR_FUSION) but make_engine built an engine with "
-                         "linear_fusion=%r" % (path, fusion, built_fusion))
-    built_soft = (bool(getattr(eng, "soft_labeling", spec.SOFT_LABELING)), str(getattr(eng, "soft_labeling_func", spec.SOFT_LABELING_FUNC)))
-    if built_soft[0] != soft[0] or (soft[0] and built_soft[1] != soft[1]):
-        raise ValueError("%s was trained with soft_labeling=%r, soft_labeling_func=%r but make_engine built an engine with "
-                         "soft_labeling=%r, soft_labeling_func=%r" % (path, soft[0], soft[1], built_soft[0], built_soft[1]))
-    built_box = str(getattr(eng, "box_cls_loss", spec.BOX_CLS_LOSS))
-    if built_box != box:
-        raise ValueError("%s was trained with box_cls_loss=%r but make_engine built an engine with box_cls_loss=%r"
-                         % (path, box, built_box))
-    if bool(getattr(eng, "siamese_backbone", True)) != mode:
-        raise ValueError("%s holds a %s model but make_engine built a %s engine (siamese_backbone=%r)"
-                         % (path, _MODE[mode], _MODE[not mode], not mode))
-    if bool(getattr(eng, "supp_roialign", True)) != pool:
-        raise ValueError("%s was trained with %s but make_engine built an engine with %s (supp_roialign=%r)"
-                         % (path, _POOL[pool], _POOL[not pool], not pool))
-    built = (bool(getattr(eng, "center_sample", spec.CENTER_SAMPLE)), str(getattr(eng, "loc_loss_type", spec.LOC_LOSS_TYPE)))
-    if built != loss:
-        raise ValueError("%s was trained with %s but make_engine built an engine with %s" % (path, _loss_name(loss), _loss_name(built)))
+    built = engine_options(eng)
+    for group, values in trained.items():
+        got = tuple(built[name] for name in spec.OPTION_GROUPS[group])
+        if spec.OPTION_RULES[group].differs(values, got):
+            raise ValueError("%s but make_engine built an engine with %s" % (_trained_with(path, group, values), spec.describe_group(group, got)))
     if "optimizer" in extras and isinstance(extras["optimizer"], dict) and "momentum_buffer" in extras["optimizer"]:
         eng.load_optimizer_state_dict(extras["optimizer"])
     return eng, int(extras.get("iteration", 0))
-
-
-_MODE = {True: "two-backbone (siamese_backbone=True)", False: "shared-backbone (siamese_backbone=False)"}
-_POOL = {True: "ROIAlign query pooling (supp_roialign=True)", False: "global-average query pooling (supp_roialign=False)"}
 
 
 _C2_BRANCH = {"branch2a": ("conv1", "bn1"), "branch2b": ("conv2", "bn2"), "branch2c": ("conv3", "bn3"),
@@ -306,8 +241,7 @@ def load_c2_resnet(path, defaults, second_stage=None, siamese_backbone=True, box
         name = translate_c2_resnet_name(k)
         if name is not None:
             loaded[name] = torch.as_tensor(blobs[k])
-    shapes = spec.hot_path_shapes(siamese_backbone)
-    box = spec.box_head_shapes(box_cls_loss=box_cls_loss, soft_labeling=soft_labeling, linear_fusion=linear_fusion)
+    shapes, box = _model_shapes(siamese_backbone, box_cls_loss, soft_labeling, linear_fusion)
     if second_stage is not False and "roi_heads.box.feature_aggreg.0.weight" in defaults:
         spec.check_linear_fusion(defaults, linear_fusion, who="the loader (defaults)")
     if second_stage or (second_stage is None and all(k in defaults for k in box)):

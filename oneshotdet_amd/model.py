@@ -382,17 +382,15 @@ class HotPathEngine(object):
 
     def __init__(self, state_dict, dtype=torch.float32, device="cuda", siamese_backbone=True, supp_roialign=True,
                  box_cls_loss="ce_loss", soft_labeling=False, soft_labeling_func="linear", linear_fusion=False, neg_support=False):
-        self.linear_fusion = bool(linear_fusion)
-        self.neg_support = spec.check_neg_support(neg_support, True, linear_fusion, box_cls_loss, soft_labeling, who="the HotPathEngine")
-        self.soft_labeling, self.soft_labeling_func = spec.soft_labeling_mode(soft_labeling, soft_labeling_func)
-        self.box_cls_loss = spec.box_cls_loss_mode(box_cls_loss, soft_labeling=self.soft_labeling)    # ValueError before anything is built
+        # spec.MODEL_OPTIONS: ValueError by name before anything is built; the rows this engine takes become attributes
+        given = spec.options_in(locals())
+        options = spec.check_options("the HotPathEngine", True, **given)
+        vars(self).update((name, getattr(options, name)) for name in given)
         if not torch.cuda.is_available():
             raise ops._lib.OsdError("HotPathEngine needs an MI355X: no GPU visible and there is no CPU fallback")
         ops._lib.load()
         self.device = torch.device(device)
         self.dtype = dtype
-        self.siamese_backbone = bool(siamese_backbone)
-        self.supp_roialign = bool(supp_roialign)
         self.sd = {k: torch.as_tensor(v).to(self.device, torch.float32) for k, v in state_dict.items()
                    if self.siamese_backbone or not spec.is_query_backbone_key(k)}
         missing = [k for k in spec.hot_path_shapes(self.siamese_backbone) if k not in self.sd]

@@ -178,22 +178,15 @@ class FCOSModule(nn.Module):
 class OneShotDetector(nn.Module):
     """GeneralizedRCNN (detector/generalized_rcnn.py:55-332) in eval mode: `backbone`, `supp_backbone`, `rpn` (and the
     `roi_heads.box.*` entries when present) under the reference's names, forward -> list[BoxList] with `scores` and
-    `labels` (= target_ids[i]) like the reference returns.  siamese_backbone=False: the shared-backbone model
-    (FEW_SHOT.SIAMESE_BACKBONE False): no `supp_backbone`, the query goes through `backbone`.  supp_roialign=False
-    (FEW_SHOT.SUPP_ROIALIGN False): the query pyramid is pooled by global average instead of the 1 x 1 ROIAlign.  box_cls_loss
-    (FEW_SHOT.SECOND_STAGE_CLS_LOSS): "ce_loss", or "focal_loss" / "mse_loss" for a model whose cls_score has one output.
-    soft_labeling / soft_labeling_func (FEW_SHOT.SOFT_LABELING / SOFT_LABELING_FUNC): admits a model trained with "l1_loss" (one output)
-    or "cxe_loss" (two).  linear_fusion (FEW_SHOT.LINEAR_FUSION): a model without compress_dim_conv whose feature_aggreg.0 reads
-    cat(x, query).  neg_support (FEW_SHOT.NEG_SUPPORT.TURN_ON): a model trained with a negative support; validated, and nothing
-    computed changes (the reference discards the negative logits in evaluation)."""
+    `labels` (= target_ids[i]) like the reference returns.  The options (spec.MODEL_OPTIONS) are model.HotPathEngine's and go to
+    it as they are: which model the state_dict is of (siamese_backbone=False: no `supp_backbone`, the query goes through
+    `backbone`) and how it was trained."""
 
     def __init__(self, state_dict, dtype=torch.float32, device="cuda", siamese_backbone=True, supp_roialign=True,
                  box_cls_loss="ce_loss", soft_labeling=False, soft_labeling_func="linear", linear_fusion=False, neg_support=False):
+        options = spec.options_in(locals())
         super(OneShotDetector, self).__init__()
-        self.engine = model.HotPathEngine(state_dict, dtype=dtype, device=device, siamese_backbone=siamese_backbone,
-                                          supp_roialign=supp_roialign, box_cls_loss=box_cls_loss, soft_labeling=soft_labeling,
-                                          soft_labeling_func=soft_labeling_func, linear_fusion=linear_fusion,
-                                          neg_support=neg_support)
+        self.engine = model.HotPathEngine(state_dict, dtype=dtype, device=device, **options)
         self.second_stage = self.engine.box_head is not None
 
     def state_dict(self, *a, **k):

@@ -6,6 +6,7 @@ config of record configs/fcos/2019_10_25_vanilla_siamse_backbone.yaml + config/d
 tests/test_spec.py checks this list against tests/golden/state_dict_keys.json, which was dumped from the real
 reference model.
 """
+import inspect
 from collections import OrderedDict, namedtuple
 
 # ---- config of record (only the values the hot path reads; SURVEY.md §5) ----
@@ -32,6 +33,8 @@ POS_RADIUS = 1.5
 CENTER_SAMPLE = True                  # yaml FCOS.CENTER_SAMPLE (defaults.py:309 has False: positives inside the whole box, loss.py:176-177)
 LOC_LOSS_TYPE = "giou"                # yaml FCOS.LOC_LOSS_TYPE (defaults.py:311 has 'iou'; iou_loss.py:36-41 also 'linear_iou')
 LOC_LOSS_TYPES = ("giou", "iou", "linear_iou")       # index = OSD_LOC_LOSS_* of include/oneshotdet_hip.h
+SIAMESE_BACKBONE = True               # yaml FEW_SHOT.SIAMESE_BACKBONE: the query has a backbone of its own (generalized_rcnn.py:69-71,274-275)
+SUPP_ROIALIGN = True                  # yaml FEW_SHOT.SUPP_ROIALIGN: the query pyramid is pooled by a 1 x 1 ROIAlign (generalized_rcnn.py:87-94)
 SIZE_DIVISIBILITY = 32
 INF = 100000000
 # second stage: yaml ROI_BOX_HEAD + defaults.py:196-229,511
@@ -199,6 +202,88 @@ def check_linear_fusion(sd, linear_fusion=False, prefix="roi_heads.box.", who="t
     return linear_fusion
 
 
+# The model's configuration options, one row each, in the order of the constructors' keywords.  A row's name is the keyword of the
+# engines and of checkpoint.resume_training, the engine's attribute and the field of a training checkpoint.
+#   config   the reference's config name
+#   default  what an engine built without the keyword has, and what a file without the field was trained with
+#   scope    "fcos_loss": the TrainEngine only (detection computes no loss); "second_stage": nothing to say about a first-stage-only run
+#   group    rows of one group are validated, compared and reported together
+#   words    how a value reads in a message next to name=value: {value: words}, a % format, or None
+ModelOption = namedtuple("ModelOption", "config default scope group words")
+MODEL_OPTIONS = OrderedDict((
+    ("siamese_backbone", ModelOption("FEW_SHOT.SIAMESE_BACKBONE", SIAMESE_BACKBONE, "model", "siamese_backbone",
+                                     {True: "the two-backbone model", False: "the shared-backbone model"})),
+    ("supp_roialign", ModelOption("FEW_SHOT.SUPP_ROIALIGN", SUPP_ROIALIGN, "model", "supp_roialign",
+                                  {True: "ROIAlign query pooling", False: "global-average query pooling"})),
+    ("center_sample", ModelOption("FCOS.CENTER_SAMPLE", CENTER_SAMPLE, "fcos_loss", "fcos_loss",
+                                  {True: "the centre-sampled", False: "the whole-box"})),
+    ("loc_loss_type", ModelOption("FCOS.LOC_LOSS_TYPE", LOC_LOSS_TYPE, "fcos_loss", "fcos_loss", "%s FCOS loss")),
+    ("box_cls_loss", ModelOption("FEW_SHOT.SECOND_STAGE_CLS_LOSS", BOX_CLS_LOSS, "second_stage", "box_cls_loss", None)),
+    ("soft_labeling", ModelOption("FEW_SHOT.SOFT_LABELING", SOFT_LABELING, "second_stage", "soft_labels", None)),
+    ("soft_labeling_func", ModelOption("FEW_SHOT.SOFT_LABELING_FUNC", SOFT_LABELING_FUNC, "second_stage", "soft_labels", None)),
+    ("linear_fusion", ModelOption("FEW_SHOT.LINEAR_FUSION", LINEAR_FUSION, "second_stage", "linear_fusion", None)),
+    ("neg_support", ModelOption("FEW_SHOT.NEG_SUPPORT.TURN_ON", NEG_SUPPORT, "second_stage", "neg_support", None)),
+))
+ModelOptions = namedtuple("ModelOptions", tuple(MODEL_OPTIONS))
+OPTION_GROUPS = OrderedDict((g, tuple(n for n, row in MODEL_OPTIONS.items() if row.group == g))       # group -> its rows' names
+                            for g in OrderedDict.fromkeys(row.group for row in MODEL_OPTIONS.values()))
+# How a file's record of one group is held against a caller's expectation or a built engine (checkpoint.resume_training):
+#   validate  (the file's record, *values) -> the values as their validator returns them, ValueError by name
+#   differs   (the file's values, the other values) -> bool
+#   absent    None, or (the file's state_dict, a DataParallel prefix stripped) -> the values of a file that does not record them
+#   why       what resuming the file with other values would do
+OptionRule = namedtuple("OptionRule", "validate differs absent why")
+_PLAIN = OptionRule(lambda record, *values: values, lambda trained, other: trained != other, None, "continue another run")
+OPTION_RULES = dict.fromkeys(OPTION_GROUPS, _PLAIN)
+OPTION_RULES.update(
+    siamese_backbone=_PLAIN._replace(absent=lambda sd: (any(k.startswith("supp_backbone.") for k in sd),),
+                                     why="tie or untie the query backbone's weights"),
+    fcos_loss=_PLAIN._replace(validate=lambda record, *values: loss_mode(*values)),
+    # validated against the soft labels of the FILE: 'l1_loss' / 'cxe_loss' exist with them only
+    box_cls_loss=_PLAIN._replace(validate=lambda record, loss: (box_cls_loss_mode(loss, soft_labeling=record["soft_labeling"]),)),
+    # the function only matters where soft labels are on
+    soft_labels=_PLAIN._replace(validate=lambda record, *values: soft_labeling_mode(*values),
+                                differs=lambda trained, other: trained[0] != other[0] or (trained[0] and trained[1] != other[1])))
+
+
+def options_in(keywords):
+    """The options among a mapping of keywords (a constructor's locals()), by name."""
+    return {name: keywords[name] for name in MODEL_OPTIONS if name in keywords}
+
+
+def check_options(who, second_stage, box_sd=None, box_prefix="roi_heads.box.", **options):
+    """-> ModelOptions: the validated values of the options given, the rows' defaults for the others.  ValueError by name, from the
+    options' own validators in the constructors' order: neg_support, the FCOS loss, the soft labels, box_cls_loss.  box_sd: a
+    state_dict that holds the box head; its layout is checked against linear_fusion before box_cls_loss is looked at and its
+    cls_score against box_cls_loss after (BoxHeadWeights)."""
+    o = ModelOptions(**dict(((name, row.default) for name, row in MODEL_OPTIONS.items()), **options))._asdict()    # another name: TypeError
+    o["neg_support"] = check_neg_support(o["neg_support"], second_stage, o["linear_fusion"], o["box_cls_loss"], o["soft_labeling"], who=who)
+    o["center_sample"], o["loc_loss_type"] = loss_mode(o["center_sample"], o["loc_loss_type"])
+    o["soft_labeling"], o["soft_labeling_func"] = soft_labeling_mode(o["soft_labeling"], o["soft_labeling_func"])
+    if box_sd is not None:
+        check_linear_fusion(box_sd, o["linear_fusion"], box_prefix)
+    o["box_cls_loss"] = box_cls_loss_mode(o["box_cls_loss"], soft_labeling=o["soft_labeling"])
+    if box_sd is not None:
+        check_box_cls_score(box_sd, o["box_cls_loss"], box_prefix, soft_labeling=o["soft_labeling"])     # a 1-row cls_score must never be read as two logits
+    return ModelOptions(**{name: type(MODEL_OPTIONS[name].default)(v) for name, v in o.items()})
+
+
+def group_values(group, record, said=None):
+    """The validated values of one group's rows in `record` ({name: value}, every row); with `said` ({name: value or None}), what is
+    said put over the record's."""
+    names = OPTION_GROUPS[group]
+    values = OPTION_RULES[group].validate(record, *(record[n] if said is None or said.get(n) is None else said[n] for n in names))
+    return tuple(type(MODEL_OPTIONS[n].default)(v) for n, v in zip(names, values))
+
+
+def describe_group(group, values, words=True):
+    """'the whole-box iou FCOS loss (center_sample=False, loc_loss_type='iou')', 'neg_support=True'; words=False: the keywords only."""
+    names = OPTION_GROUPS[group]
+    keywords = ", ".join("%s=%r" % nv for nv in zip(names, values))
+    said = [w[v] if isinstance(w, dict) else w % v for w, v in zip((MODEL_OPTIONS[n].words for n in names), values) if w]
+    return "%s (%s)" % (" ".join(said), keywords) if words and said else keywords
+
+
 def _bn(prefix, n, out):
     for k in ("weight", "bias", "running_mean", "running_var"):
         out[prefix + "." + k] = (n,)
@@ -317,6 +402,10 @@ def full_model_shapes(siamese_backbone=True, box_cls_loss="ce_loss", soft_labeli
     out = hot_path_shapes(siamese_backbone)
     out.update(box_head_shapes(box_cls_loss=box_cls_loss, soft_labeling=soft_labeling, linear_fusion=linear_fusion))
     return out
+
+
+# the options that decide a key or a shape: the keywords of full_model_shapes and of the loaders (checkpoint.py)
+SHAPE_OPTIONS = tuple(inspect.signature(full_model_shapes).parameters)
 
 
 def is_query_backbone_key(key):

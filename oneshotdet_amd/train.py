@@ -114,13 +114,8 @@ class TrainEngine(ForwardPass, BackwardPass, SecondStage, Update, State):
                  exchange_single_rank=False, grad_wire_dtype=None, siamese_backbone=True, supp_roialign=True,
                  center_sample=True, loc_loss_type="giou", box_cls_loss="ce_loss", soft_labeling=False, soft_labeling_func="linear",
                  linear_fusion=False, neg_support=False):
-        self.linear_fusion = bool(linear_fusion)
-        # ValueError by name before anything is built: the combinations FEW_SHOT.NEG_SUPPORT does not exist in
-        self.neg_support = spec.check_neg_support(neg_support, second_stage, linear_fusion, box_cls_loss, soft_labeling,
-                                                  who="the TrainEngine")
-        self.center_sample, self.loc_loss_type = spec.loss_mode(center_sample, loc_loss_type)     # ValueError before anything is built
-        self.soft_labeling, self.soft_labeling_func = spec.soft_labeling_mode(soft_labeling, soft_labeling_func)
-        self.box_cls_loss = spec.box_cls_loss_mode(box_cls_loss, soft_labeling=self.soft_labeling)
+        # spec.MODEL_OPTIONS: ValueError by name before anything is built; every row becomes an attribute
+        vars(self).update(spec.check_options("the TrainEngine", second_stage, **spec.options_in(locals()))._asdict())
         if not torch.cuda.is_available():
             raise ops._lib.OsdError("TrainEngine needs an MI355X: no GPU visible and there is no CPU fallback")
         ops._lib.load()
@@ -151,8 +146,6 @@ class TrainEngine(ForwardPass, BackwardPass, SecondStage, Update, State):
         self.split_levels = os.environ.get("OSD_SPLIT_LEVELS", "0") != "0"
         # the sum of the two towers' input gradients inside the cls tower's last data-gradient conv (A/B: OSD_NO_HEAD_SUM_FUSION=1)
         self.fuse_head_sum = os.environ.get("OSD_NO_HEAD_SUM_FUSION", "0") == "0"
-        self.siamese_backbone = bool(siamese_backbone)
-        self.supp_roialign = bool(supp_roialign)
         if not self.siamese_backbone:
             # (target, query) branch prefixes: both run on the shared backbone's convs
             self.BBS = ("backbone.", "backbone.")

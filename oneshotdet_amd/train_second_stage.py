@@ -33,7 +33,7 @@ class SecondStage(object):
             keys = torch.rand((n, P), device=self.device, dtype=torch.float32)
         # FEW_SHOT.SOFT_LABELING: the soft labels travel from the sampler to the loss (loss.py:260-287,333-334) when the loss reads
         # them; 'ce_loss' / 'focal_loss' never do, and make the launches they make without the option
-        soft = spec.box_loss_reads_soft_labels(self.box_cls_loss, getattr(self, "soft_labeling", False))
+        soft = spec.box_loss_reads_soft_labels(self.box_cls_loss, self.soft_labeling)
         ss = None
         if soft:
             sb, sl, st, si, sc, ss = ops.box_match_sample(pb, pc, gt_boxes, gt_count, keys, S, spec.BOX_POSITIVE_FRACTION,
@@ -44,12 +44,12 @@ class SecondStage(object):
                                                       spec.BOX_FG_IOU_THRESH, spec.BOX_REG_WEIGHTS)
         M = n * S
         slope, gr, eps = spec.BOX_LEAKY_SLOPE, spec.GN_GROUPS, spec.GN_EPS
-        linear = getattr(self, "linear_fusion", False)
+        linear = self.linear_fusion
         neg = neg_qfeats is not None
-        if neg != bool(getattr(self, "neg_support", False)):
+        if neg != self.neg_support:
             raise ValueError("neg_qfeats (FEW_SHOT.NEG_SUPPORT) is passed exactly when the engine was built with neg_support=True")
         if neg and (shots != 1 or linear or self.box_cls_loss != "ce_loss"):
-            spec.check_neg_support(True, True, linear, self.box_cls_loss, getattr(self, "soft_labeling", False), shots)
+            spec.check_neg_support(True, True, linear, self.box_cls_loss, self.soft_labeling, shots)
         (g2, dg2), (b2, db2) = self.extra[b + "feature_aggreg.1.weight"], self.extra[b + "feature_aggreg.1.bias"]
         if linear:
             # FEW_SHOT.LINEAR_FUSION (box_head.py:61-72,148): the split 3x3 conv takes the place of the split 1x1 conv, its

@@ -15,7 +15,7 @@ class State(object):
         state_dict(), named_grads() and the optimizer state alike."""
         h, b = "rpn.head.", "roi_heads.box."
         c, mid, p = spec.FPN_OUT, spec.FPN_OUT // 2, spec.BOX_POOL
-        nc = spec.box_cls_logits(getattr(self, "box_cls_loss", spec.BOX_CLS_LOSS), getattr(self, "soft_labeling", spec.SOFT_LABELING))    # rows of cls_score at the head of the predictor
+        nc = spec.box_cls_logits(self.box_cls_loss, self.soft_labeling)    # rows of cls_score at the head of the predictor
         nr = 4 * spec.BOX_NUM_CLASSES                                                 # rows of bbox_pred behind them
         out = {}
         for name, shape in self._plan:

@@ -15,6 +15,7 @@ import pytest
 import torch
 
 import box_cls_loss_ref as bcl
+from fake_engine import FakeEngine
 import golden_utils as gu
 from oneshotdet_amd import checkpoint, spec, synth
 from oracle import box_train_ref as obt
@@ -165,29 +166,10 @@ def test_unknown_and_out_of_scope_names_raise():
         spec.check_box_cls_score(two, "focal_loss")
 
 
-class _FakeEngine(object):
-    """What save_training_checkpoint / resume_training use of a TrainEngine (the engine itself needs the GPU)."""
-
-    def __init__(self, sd, box_cls_loss=None):
-        self.sd, self.siamese_backbone, self.supp_roialign, self.opt_state = dict(sd), True, True, None
-        if box_cls_loss is not None:
-            self.box_cls_loss = box_cls_loss
-
-    def state_dict(self):
-        return dict(self.sd)
-
-    def optimizer_state_dict(self):
-        return {"momentum_buffer": {k: torch.zeros_like(v) for k, v in self.sd.items()}, "steps": 3, "lr": 0.01,
-                "momentum": 0.9, "weight_decay": 1e-4}
-
-    def load_optimizer_state_dict(self, st):
-        self.opt_state = st
-
-
 def test_checkpoint_records_the_mode_and_refuses_a_mismatch(tmp_path):
     sd = {k: torch.from_numpy(v) for k, v in synth.make_state_dict(spec.full_model_shapes(box_cls_loss="focal_loss")).items()}
     p = str(tmp_path / "model_0000010.pth")
-    checkpoint.save_training_checkpoint(p, _FakeEngine(sd, "focal_loss"), 10)
+    checkpoint.save_training_checkpoint(p, FakeEngine(sd, box_cls_loss="focal_loss"), 10)
     raw = torch.load(p, map_location="cpu", weights_only=False)
     assert raw["box_cls_loss"] == "focal_loss" and raw["loc_loss_type"] == "giou"
     # .pth round trip in the new shapes
@@ -196,9 +178,9 @@ def test_checkpoint_records_the_mode_and_refuses_a_mismatch(tmp_path):
     assert back["roi_heads.box.predictor.cls_score.weight"].shape == (1, 1024)
     with pytest.raises(ValueError, match="cls_score"):                  # the default mode's shapes do not fit the file
         checkpoint.load_checkpoint(p)
-    eng, it = checkpoint.resume_training(p, lambda s: _FakeEngine(s, "focal_loss"), box_cls_loss="focal_loss")
+    eng, it = checkpoint.resume_training(p, lambda s: FakeEngine(s, box_cls_loss="focal_loss"), box_cls_loss="focal_loss")
     assert it == 10 and eng.opt_state["steps"] == 3 and all(torch.equal(eng.sd[k], sd[k]) for k in sd)
-    checkpoint.resume_training(p, lambda s: _FakeEngine(s, "focal_loss"))        # the caller need not say it: the file does
+    checkpoint.resume_training(p, lambda s: FakeEngine(s, box_cls_loss="focal_loss"))        # the caller need not say it: the file does
     called = []
     for other in ("ce_loss", "mse_loss"):       # refused before make_engine, naming both values
         with pytest.raises(ValueError) as e:
@@ -209,21 +191,21 @@ def test_checkpoint_records_the_mode_and_refuses_a_mismatch(tmp_path):
         checkpoint.resume_training(p, lambda s: called.append(1), box_cls_loss="l1_loss")
     # the two one-logit modes share their shapes: only the record tells them apart (make_engine built the other one)
     with pytest.raises(ValueError) as e:
-        checkpoint.resume_training(p, lambda s: _FakeEngine(s, "mse_loss"))
+        checkpoint.resume_training(p, lambda s: FakeEngine(s, box_cls_loss="mse_loss"))
     assert "box_cls_loss='focal_loss'" in str(e.value) and "box_cls_loss='mse_loss'" in str(e.value)
     # a file without the field (every file written before) and an engine without the attribute are 'ce_loss'
     sd2 = {k: torch.from_numpy(v) for k, v in synth.make_state_dict(spec.full_model_shapes()).items()}
     p2 = str(tmp_path / "model_old.pth")
-    checkpoint.save_training_checkpoint(p2, _FakeEngine(sd2), 7)
+    checkpoint.save_training_checkpoint(p2, FakeEngine(sd2), 7)
     raw2 = torch.load(p2, map_location="cpu", weights_only=False)
     assert raw2["box_cls_loss"] == "ce_loss"
     del raw2["box_cls_loss"]
     torch.save(raw2, p2)
-    eng, it = checkpoint.resume_training(p2, lambda s: _FakeEngine(s), box_cls_loss="ce_loss")
+    eng, it = checkpoint.resume_training(p2, lambda s: FakeEngine(s), box_cls_loss="ce_loss")
     assert it == 7
-    checkpoint.resume_training(p2, lambda s: _FakeEngine(s, "ce_loss"))
+    checkpoint.resume_training(p2, lambda s: FakeEngine(s, box_cls_loss="ce_loss"))
     with pytest.raises(ValueError, match="box_cls_loss='ce_loss'"):
-        checkpoint.resume_training(p2, lambda s: _FakeEngine(s), box_cls_loss="focal_loss")
+        checkpoint.resume_training(p2, lambda s: FakeEngine(s), box_cls_loss="focal_loss")
 
 
 def test_c_entries_refuse_a_bad_mode_or_stride():

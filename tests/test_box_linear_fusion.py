@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 import torch
 
+from fake_engine import FakeEngine
 import box_linear_fusion_ref as blf
 import golden_utils as gu
 from oneshotdet_amd import checkpoint, spec, synth
@@ -70,29 +71,10 @@ def test_a_state_dict_of_the_other_setting_is_refused_by_name():
         BoxHeadWeights(std, torch.float32, linear_fusion=True)
 
 
-class _FakeEngine(object):
-    """What save_training_checkpoint / resume_training use of a TrainEngine (the engine itself needs the GPU)."""
-
-    def __init__(self, sd, linear_fusion=None):
-        self.sd, self.siamese_backbone, self.supp_roialign, self.opt_state = dict(sd), True, True, None
-        if linear_fusion is not None:
-            self.linear_fusion = linear_fusion
-
-    def state_dict(self):
-        return dict(self.sd)
-
-    def optimizer_state_dict(self):
-        return {"momentum_buffer": {k: torch.zeros_like(v) for k, v in self.sd.items()}, "steps": 3, "lr": 0.01,
-                "momentum": 0.9, "weight_decay": 1e-4}
-
-    def load_optimizer_state_dict(self, st):
-        self.opt_state = st
-
-
 def test_checkpoint_round_trip_and_resume_refusal(tmp_path):
     sd = {k: torch.from_numpy(v) for k, v in synth.make_state_dict(spec.full_model_shapes(linear_fusion=True)).items()}
     p = str(tmp_path / "model_0000010.pth")
-    checkpoint.save_training_checkpoint(p, _FakeEngine(sd, True), 10)
+    checkpoint.save_training_checkpoint(p, FakeEngine(sd, linear_fusion=True), 10)
     raw = torch.load(p, map_location="cpu", weights_only=False)
     assert raw["linear_fusion"] is True and not any("compress_dim_conv" in k for k in raw["model"])
     back, extras = checkpoint.load_checkpoint(p, linear_fusion=True)
@@ -107,27 +89,27 @@ def test_checkpoint_round_trip_and_resume_refusal(tmp_path):
     with pytest.raises(ValueError, match=r"FEW_SHOT\.LINEAR_FUSION True"):
         checkpoint.load_checkpoint(p3)
     assert list(checkpoint.load_checkpoint(p3, linear_fusion=True)[0].keys()) == list(back.keys())
-    eng, it = checkpoint.resume_training(p, lambda s: _FakeEngine(s, True), linear_fusion=True)
+    eng, it = checkpoint.resume_training(p, lambda s: FakeEngine(s, linear_fusion=True), linear_fusion=True)
     assert it == 10 and eng.opt_state["steps"] == 3
-    checkpoint.resume_training(p, lambda s: _FakeEngine(s, True))          # the caller need not say it: the file does
+    checkpoint.resume_training(p, lambda s: FakeEngine(s, linear_fusion=True))          # the caller need not say it: the file does
     called = []
     with pytest.raises(ValueError) as e:                                   # refused before make_engine, naming both values
         checkpoint.resume_training(p, lambda s: called.append(1), linear_fusion=False)
     assert "linear_fusion=True" in str(e.value) and "linear_fusion=False" in str(e.value) and not called
     with pytest.raises(ValueError, match="make_engine built an engine with linear_fusion=False"):
-        checkpoint.resume_training(p, lambda s: _FakeEngine(s))
+        checkpoint.resume_training(p, lambda s: FakeEngine(s))
     # the default model: the field is recorded as False, a file without it means False, and loads as before
     sd2 = {k: torch.from_numpy(v) for k, v in synth.make_state_dict(spec.full_model_shapes()).items()}
     p2 = str(tmp_path / "model_old.pth")
-    checkpoint.save_training_checkpoint(p2, _FakeEngine(sd2), 7)
+    checkpoint.save_training_checkpoint(p2, FakeEngine(sd2), 7)
     raw2 = torch.load(p2, map_location="cpu", weights_only=False)
     assert raw2["linear_fusion"] is False
     del raw2["linear_fusion"]
     torch.save(raw2, p2)
-    eng, it = checkpoint.resume_training(p2, lambda s: _FakeEngine(s), linear_fusion=False)
+    eng, it = checkpoint.resume_training(p2, lambda s: FakeEngine(s), linear_fusion=False)
     assert it == 7 and list(eng.sd.keys()) == list(spec.full_model_shapes().keys())
     with pytest.raises(ValueError, match="linear_fusion=False.*linear_fusion=True"):
-        checkpoint.resume_training(p2, lambda s: _FakeEngine(s, True), linear_fusion=True)
+        checkpoint.resume_training(p2, lambda s: FakeEngine(s, linear_fusion=True), linear_fusion=True)
     with pytest.raises(ValueError, match=r"FEW_SHOT\.LINEAR_FUSION False.*linear_fusion=False"):
         checkpoint.load_checkpoint(p2, linear_fusion=True)
 

@@ -13,6 +13,7 @@ import torch
 
 import box_cls_loss_ref as bcl
 import box_neg_support_ref as bns
+from fake_engine import FakeEngine
 import golden_utils as gu
 from oneshotdet_amd import checkpoint, spec, synth
 from oracle import box_train_ref as obt
@@ -244,53 +245,34 @@ def test_the_option_changes_no_key_and_no_shape():
     assert mine[P + "predictor.cls_score.weight"][0] == 2
 
 
-class _FakeEngine(object):
-    """What save_training_checkpoint / resume_training use of a TrainEngine (the engine itself needs the GPU)."""
-
-    def __init__(self, sd, neg_support=None):
-        self.sd, self.siamese_backbone, self.supp_roialign, self.opt_state = dict(sd), True, True, None
-        if neg_support is not None:
-            self.neg_support = neg_support
-
-    def state_dict(self):
-        return dict(self.sd)
-
-    def optimizer_state_dict(self):
-        return {"momentum_buffer": {k: torch.zeros_like(v) for k, v in self.sd.items()}, "steps": 3, "lr": 0.01,
-                "momentum": 0.9, "weight_decay": 1e-4}
-
-    def load_optimizer_state_dict(self, st):
-        self.opt_state = st
-
-
 def test_checkpoint_round_trip_and_resume_refusal(tmp_path):
     sd = {k: torch.from_numpy(v) for k, v in synth.make_state_dict(spec.full_model_shapes()).items()}
     p = str(tmp_path / "model_0000010.pth")
-    checkpoint.save_training_checkpoint(p, _FakeEngine(sd, True), 10)
+    checkpoint.save_training_checkpoint(p, FakeEngine(sd, neg_support=True), 10)
     raw = torch.load(p, map_location="cpu", weights_only=False)
     assert raw["neg_support"] is True and list(raw["model"].keys()) == list(spec.full_model_shapes().keys())
     back, extras = checkpoint.load_checkpoint(p)                               # the weights interchange with the plain model's
     assert extras["neg_support"] is True and all(torch.equal(back[k], sd[k]) for k in sd)
-    eng, it = checkpoint.resume_training(p, lambda s: _FakeEngine(s, True), neg_support=True)
+    eng, it = checkpoint.resume_training(p, lambda s: FakeEngine(s, neg_support=True), neg_support=True)
     assert it == 10 and eng.opt_state["steps"] == 3
-    checkpoint.resume_training(p, lambda s: _FakeEngine(s, True))              # the caller need not say it: the file does
+    checkpoint.resume_training(p, lambda s: FakeEngine(s, neg_support=True))              # the caller need not say it: the file does
     called = []
     with pytest.raises(ValueError) as e:                                       # refused before make_engine, naming both values
         checkpoint.resume_training(p, lambda s: called.append(1), neg_support=False)
     assert "neg_support=True" in str(e.value) and "neg_support=False" in str(e.value) and "NEG_SUPPORT" in str(e.value) and not called
     with pytest.raises(ValueError, match=r"NEG_SUPPORT.*make_engine built an engine with neg_support=False"):
-        checkpoint.resume_training(p, lambda s: _FakeEngine(s))
+        checkpoint.resume_training(p, lambda s: FakeEngine(s))
     # the default model: recorded as False; a file without the field reads as False
     p2 = str(tmp_path / "model_old.pth")
-    checkpoint.save_training_checkpoint(p2, _FakeEngine(sd), 7)
+    checkpoint.save_training_checkpoint(p2, FakeEngine(sd), 7)
     raw2 = torch.load(p2, map_location="cpu", weights_only=False)
     assert raw2["neg_support"] is False
     del raw2["neg_support"]
     torch.save(raw2, p2)
-    eng, it = checkpoint.resume_training(p2, lambda s: _FakeEngine(s), neg_support=False)
+    eng, it = checkpoint.resume_training(p2, lambda s: FakeEngine(s), neg_support=False)
     assert it == 7
     with pytest.raises(ValueError, match=r"neg_support=False.*neg_support=True"):
-        checkpoint.resume_training(p2, lambda s: _FakeEngine(s, True), neg_support=True)
+        checkpoint.resume_training(p2, lambda s: FakeEngine(s, neg_support=True), neg_support=True)
 
 
 def test_documents_describe_the_option():

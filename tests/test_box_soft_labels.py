@@ -16,6 +16,7 @@ import torch
 
 import box_cls_loss_ref as bcl
 import box_soft_label_ref as bsl
+from fake_engine import FakeEngine
 import golden_utils as gu
 from oneshotdet_amd import checkpoint, spec, synth
 
@@ -170,32 +171,12 @@ def test_spec_accepts_the_soft_losses_with_soft_labeling_only(fx):
         spec.box_cls_loss_mode("hinge", soft_labeling=True)
 
 
-class _FakeEngine(object):
-    """What save_training_checkpoint / resume_training use of a TrainEngine (the engine itself needs the GPU)."""
-
-    def __init__(self, sd, box_cls_loss=None, soft_labeling=None, soft_labeling_func=None):
-        self.sd, self.siamese_backbone, self.supp_roialign, self.opt_state = dict(sd), True, True, None
-        for k, v in (("box_cls_loss", box_cls_loss), ("soft_labeling", soft_labeling), ("soft_labeling_func", soft_labeling_func)):
-            if v is not None:
-                setattr(self, k, v)
-
-    def state_dict(self):
-        return dict(self.sd)
-
-    def optimizer_state_dict(self):
-        return {"momentum_buffer": {k: torch.zeros_like(v) for k, v in self.sd.items()}, "steps": 3, "lr": 0.01,
-                "momentum": 0.9, "weight_decay": 1e-4}
-
-    def load_optimizer_state_dict(self, st):
-        self.opt_state = st
-
-
 def test_checkpoint_records_both_options_and_refuses_a_mismatch(tmp_path):
     sd = {k: torch.from_numpy(v) for k, v in synth.make_state_dict(spec.full_model_shapes(box_cls_loss="l1_loss", soft_labeling=True)).items()}
     p = str(tmp_path / "model_0000010.pth")
 
     def make(func="transLinear", soft=True, loss="l1_loss"):
-        return lambda s: _FakeEngine(s, loss, soft, func)
+        return lambda s: FakeEngine(s, box_cls_loss=loss, soft_labeling=soft, soft_labeling_func=func)
     checkpoint.save_training_checkpoint(p, make()(sd), 10)
     raw = torch.load(p, map_location="cpu", weights_only=False)
     assert raw["soft_labeling"] is True and raw["soft_labeling_func"] == "transLinear" and raw["box_cls_loss"] == "l1_loss"
@@ -223,18 +204,18 @@ def test_checkpoint_records_both_options_and_refuses_a_mismatch(tmp_path):
     # a file without the fields (every file written before) was trained with (False, "linear")
     sd2 = {k: torch.from_numpy(v) for k, v in synth.make_state_dict(spec.full_model_shapes(box_cls_loss="mse_loss")).items()}
     p2 = str(tmp_path / "model_old.pth")
-    checkpoint.save_training_checkpoint(p2, _FakeEngine(sd2, "mse_loss"), 7)
+    checkpoint.save_training_checkpoint(p2, FakeEngine(sd2, box_cls_loss="mse_loss"), 7)
     raw2 = torch.load(p2, map_location="cpu", weights_only=False)
     assert raw2["soft_labeling"] is False and raw2["soft_labeling_func"] == "linear"
     del raw2["soft_labeling"], raw2["soft_labeling_func"]
     torch.save(raw2, p2)
-    eng, it = checkpoint.resume_training(p2, lambda s: _FakeEngine(s, "mse_loss"), soft_labeling=False)
+    eng, it = checkpoint.resume_training(p2, lambda s: FakeEngine(s, box_cls_loss="mse_loss"), soft_labeling=False)
     assert it == 7
-    checkpoint.resume_training(p2, lambda s: _FakeEngine(s, "mse_loss"), soft_labeling_func="transLinear")    # the function is moot without soft labels
+    checkpoint.resume_training(p2, lambda s: FakeEngine(s, box_cls_loss="mse_loss"), soft_labeling_func="transLinear")    # the function is moot without soft labels
     with pytest.raises(ValueError, match="soft_labeling=False, soft_labeling_func='linear'.*soft_labeling=True"):
-        checkpoint.resume_training(p2, lambda s: _FakeEngine(s, "mse_loss", True), soft_labeling=True)
+        checkpoint.resume_training(p2, lambda s: FakeEngine(s, box_cls_loss="mse_loss", soft_labeling=True), soft_labeling=True)
     with pytest.raises(ValueError, match="make_engine built an engine with soft_labeling=True"):
-        checkpoint.resume_training(p2, lambda s: _FakeEngine(s, "mse_loss", True))
+        checkpoint.resume_training(p2, lambda s: FakeEngine(s, box_cls_loss="mse_loss", soft_labeling=True))
 
 
 def test_c_entries_refuse_bad_arguments_before_any_launch():

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import fcos_loss_ref as flr
+from fake_engine import FakeEngine
 import golden_utils as gu
 from oneshotdet_amd import checkpoint, spec, synth
 from oracle import hotpath_ref as orc
@@ -164,36 +165,17 @@ def test_c_entries_reject_a_bad_loss_type_before_any_launch():
                                     0, None) == 0
 
 
-class _FakeEngine(object):
-    """What save_training_checkpoint / resume_training use of a TrainEngine (the engine itself needs the GPU)."""
-
-    def __init__(self, sd, mode=None):
-        self.sd, self.siamese_backbone, self.supp_roialign, self.opt_state = dict(sd), True, True, None
-        if mode is not None:
-            self.center_sample, self.loc_loss_type = mode
-
-    def state_dict(self):
-        return dict(self.sd)
-
-    def optimizer_state_dict(self):
-        return {"momentum_buffer": {k: torch.zeros_like(v) for k, v in self.sd.items()}, "steps": 3, "lr": 0.01,
-                "momentum": 0.9, "weight_decay": 1e-4}
-
-    def load_optimizer_state_dict(self, st):
-        self.opt_state = st
-
-
 def test_training_checkpoint_records_the_loss_and_refuses_a_mismatch(tmp_path):
     sd = {k: torch.from_numpy(v) for k, v in synth.make_state_dict(spec.hot_path_shapes()).items()}
     mode = (False, "iou")
     p = str(tmp_path / "model_0000010.pth")
-    checkpoint.save_training_checkpoint(p, _FakeEngine(sd, mode), 10)
+    checkpoint.save_training_checkpoint(p, FakeEngine(sd, center_sample=mode[0], loc_loss_type=mode[1]), 10)
     raw = torch.load(p, map_location="cpu", weights_only=False)
     assert raw["center_sample"] is False and raw["loc_loss_type"] == "iou" and raw["supp_roialign"] is True
-    eng, it = checkpoint.resume_training(p, lambda s: _FakeEngine(s, mode), center_sample=False, loc_loss_type="iou")
+    eng, it = checkpoint.resume_training(p, lambda s: FakeEngine(s, center_sample=mode[0], loc_loss_type=mode[1]), center_sample=False, loc_loss_type="iou")
     assert it == 10 and eng.opt_state["steps"] == 3 and all(torch.equal(eng.sd[k], sd[k]) for k in sd)
-    checkpoint.resume_training(p, lambda s: _FakeEngine(s, mode))               # the caller need not say it: the file does
-    checkpoint.resume_training(p, lambda s: _FakeEngine(s, mode), loc_loss_type="iou")
+    checkpoint.resume_training(p, lambda s: FakeEngine(s, center_sample=mode[0], loc_loss_type=mode[1]))               # the caller need not say it: the file does
+    checkpoint.resume_training(p, lambda s: FakeEngine(s, center_sample=mode[0], loc_loss_type=mode[1]), loc_loss_type="iou")
     # the caller expects another loss: refused before make_engine, naming both
     called = []
     for kw in ({"center_sample": True}, {"loc_loss_type": "giou"}, {"center_sample": True, "loc_loss_type": "linear_iou"}):
@@ -209,28 +191,28 @@ def test_training_checkpoint_records_the_loss_and_refuses_a_mismatch(tmp_path):
     # make_engine builds another loss than the file's: refused after it, naming both
     for other in ((True, "giou"), (False, "giou"), (True, "iou")):
         with pytest.raises(ValueError) as e:
-            checkpoint.resume_training(p, lambda s: _FakeEngine(s, other))
+            checkpoint.resume_training(p, lambda s: FakeEngine(s, center_sample=other[0], loc_loss_type=other[1]))
         assert "whole-box iou" in str(e.value) and "center_sample=%r, loc_loss_type=%r" % other in str(e.value)
     # the weights' keys do not depend on the loss
     p2 = str(tmp_path / "model_default.pth")
-    checkpoint.save_training_checkpoint(p2, _FakeEngine(sd, (True, "giou")), 5)
+    checkpoint.save_training_checkpoint(p2, FakeEngine(sd, center_sample=True, loc_loss_type="giou"), 5)
     a, _ = checkpoint.load_checkpoint(p)
     b, _ = checkpoint.load_checkpoint(p2)
     assert list(a) == list(b) and all(torch.equal(a[k], b[k]) for k in a)
     # an engine without the attributes is the default mode; a file without the fields (every file written before) is (True, "giou")
     p3 = str(tmp_path / "model_old.pth")
-    checkpoint.save_training_checkpoint(p3, _FakeEngine(sd), 7)
+    checkpoint.save_training_checkpoint(p3, FakeEngine(sd), 7)
     raw3 = torch.load(p3, map_location="cpu", weights_only=False)
     assert raw3["center_sample"] is True and raw3["loc_loss_type"] == "giou"
     del raw3["center_sample"], raw3["loc_loss_type"]
     torch.save(raw3, p3)
-    eng, it = checkpoint.resume_training(p3, lambda s: _FakeEngine(s), center_sample=True, loc_loss_type="giou")
+    eng, it = checkpoint.resume_training(p3, lambda s: FakeEngine(s), center_sample=True, loc_loss_type="giou")
     assert it == 7
-    checkpoint.resume_training(p3, lambda s: _FakeEngine(s, (True, "giou")))
+    checkpoint.resume_training(p3, lambda s: FakeEngine(s, center_sample=True, loc_loss_type="giou"))
     with pytest.raises(ValueError, match="centre-sampled giou"):
-        checkpoint.resume_training(p3, lambda s: _FakeEngine(s, mode), center_sample=False, loc_loss_type="iou")
+        checkpoint.resume_training(p3, lambda s: FakeEngine(s, center_sample=mode[0], loc_loss_type=mode[1]), center_sample=False, loc_loss_type="iou")
     with pytest.raises(ValueError, match="centre-sampled giou"):
-        checkpoint.resume_training(p3, lambda s: _FakeEngine(s, mode))
+        checkpoint.resume_training(p3, lambda s: FakeEngine(s, center_sample=mode[0], loc_loss_type=mode[1]))
     # plain save_checkpoint is untouched: weights only
     p4 = str(tmp_path / "weights.pth")
     checkpoint.save_checkpoint(p4, sd)

@@ -10,6 +10,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+from fake_engine import FakeEngine
 import golden_utils as gu
 from oneshotdet_amd import checkpoint, spec, synth
 from oracle import hotpath_ref as orc
@@ -126,57 +127,38 @@ def test_oracle_training_matches_reference(name, shared, avgpool):
     assert checked == 2 * (16 if shared else 19) and query == (0 if shared else 5), (checked, query)
 
 
-class _FakeEngine(object):
-    """What save_training_checkpoint / resume_training use of a TrainEngine (the engine itself needs the GPU)."""
-
-    def __init__(self, sd, supp_roialign=None):
-        self.sd, self.siamese_backbone, self.opt_state = dict(sd), True, None
-        if supp_roialign is not None:
-            self.supp_roialign = supp_roialign
-
-    def state_dict(self):
-        return dict(self.sd)
-
-    def optimizer_state_dict(self):
-        return {"momentum_buffer": {k: torch.zeros_like(v) for k, v in self.sd.items()}, "steps": 3, "lr": 0.01,
-                "momentum": 0.9, "weight_decay": 1e-4}
-
-    def load_optimizer_state_dict(self, st):
-        self.opt_state = st
-
-
 def test_training_checkpoint_records_the_pooling_and_refuses_a_mismatch(tmp_path):
     sd = {k: torch.from_numpy(v) for k, v in synth.make_state_dict(spec.hot_path_shapes()).items()}
     p = str(tmp_path / "model_0000010.pth")
-    checkpoint.save_training_checkpoint(p, _FakeEngine(sd, False), 10)
+    checkpoint.save_training_checkpoint(p, FakeEngine(sd, supp_roialign=False), 10)
     raw = torch.load(p, map_location="cpu", weights_only=False)
     assert raw["supp_roialign"] is False and raw["siamese_backbone"] is True
-    eng, it = checkpoint.resume_training(p, lambda s: _FakeEngine(s, False), supp_roialign=False)
+    eng, it = checkpoint.resume_training(p, lambda s: FakeEngine(s, supp_roialign=False), supp_roialign=False)
     assert it == 10 and eng.opt_state["steps"] == 3 and all(torch.equal(eng.sd[k], sd[k]) for k in sd)
-    checkpoint.resume_training(p, lambda s: _FakeEngine(s, False))          # the caller need not say it: the file does
+    checkpoint.resume_training(p, lambda s: FakeEngine(s, supp_roialign=False))          # the caller need not say it: the file does
     with pytest.raises(ValueError, match="global-average"):
-        checkpoint.resume_training(p, lambda s: _FakeEngine(s, True), supp_roialign=True)
+        checkpoint.resume_training(p, lambda s: FakeEngine(s, supp_roialign=True), supp_roialign=True)
     with pytest.raises(ValueError, match="supp_roialign=True"):
-        checkpoint.resume_training(p, lambda s: _FakeEngine(s, True))
+        checkpoint.resume_training(p, lambda s: FakeEngine(s, supp_roialign=True))
     # the keys are the same in both modes: load_checkpoint reads either file the same way
     p2 = str(tmp_path / "model_roialign.pth")
-    checkpoint.save_training_checkpoint(p2, _FakeEngine(sd, True), 5)
+    checkpoint.save_training_checkpoint(p2, FakeEngine(sd, supp_roialign=True), 5)
     a, _ = checkpoint.load_checkpoint(p)
     b, _ = checkpoint.load_checkpoint(p2)
     assert list(a) == list(b) and all(torch.equal(a[k], b[k]) for k in a)
     # an engine without the attribute is the default mode; a file without the field resumes as ROIAlign pooling
     p3 = str(tmp_path / "model_old.pth")
-    checkpoint.save_training_checkpoint(p3, _FakeEngine(sd), 7)
+    checkpoint.save_training_checkpoint(p3, FakeEngine(sd), 7)
     assert torch.load(p3, map_location="cpu", weights_only=False)["supp_roialign"] is True
     raw3 = torch.load(p3, map_location="cpu", weights_only=False)
     del raw3["supp_roialign"]
     torch.save(raw3, p3)
-    eng, it = checkpoint.resume_training(p3, lambda s: _FakeEngine(s, True), supp_roialign=True)
+    eng, it = checkpoint.resume_training(p3, lambda s: FakeEngine(s, supp_roialign=True), supp_roialign=True)
     assert it == 7
     with pytest.raises(ValueError, match="ROIAlign"):
-        checkpoint.resume_training(p3, lambda s: _FakeEngine(s, False), supp_roialign=False)
+        checkpoint.resume_training(p3, lambda s: FakeEngine(s, supp_roialign=False), supp_roialign=False)
     with pytest.raises(ValueError):
-        checkpoint.resume_training(p3, lambda s: _FakeEngine(s, False))
+        checkpoint.resume_training(p3, lambda s: FakeEngine(s, supp_roialign=False))
 
 
 def test_c_abi_workspace_and_refused_shapes():

@@ -11,6 +11,7 @@ import numpy as np
 import pytest
 import torch
 
+from fake_engine import FakeEngine
 import golden_utils as gu
 from oneshotdet_amd import checkpoint, spec, synth
 from oracle import hotpath_ref as orc
@@ -171,52 +172,35 @@ def test_load_c2_resnet_shared(tmp_path):
     assert torch.equal(out["rpn.head.cls_logits.bias"], defaults["rpn.head.cls_logits.bias"])
 
 
-class _FakeEngine(object):
-    """What save_training_checkpoint / resume_training use of a TrainEngine (the engine itself needs the GPU)."""
-
-    def __init__(self, sd, siamese_backbone):
-        self.sd, self.siamese_backbone, self.opt_state = dict(sd), siamese_backbone, None
-
-    def state_dict(self):
-        return dict(self.sd)
-
-    def optimizer_state_dict(self):
-        return {"momentum_buffer": {k: torch.zeros_like(v) for k, v in self.sd.items()}, "steps": 3, "lr": 0.01,
-                "momentum": 0.9, "weight_decay": 1e-4}
-
-    def load_optimizer_state_dict(self, st):
-        self.opt_state = st
-
-
 def test_training_checkpoint_round_trip_and_mode_mismatch(tmp_path):
     sd = _sd(spec.hot_path_shapes(False))
     p = str(tmp_path / "model_0000020.pth")
-    checkpoint.save_training_checkpoint(p, _FakeEngine(sd, False), 20)
+    checkpoint.save_training_checkpoint(p, FakeEngine(sd, siamese_backbone=False), 20)
     raw = torch.load(p, map_location="cpu", weights_only=False)
     assert raw["siamese_backbone"] is False and raw["iteration"] == 20
     assert not any(k.startswith("supp_backbone.") for k in raw["model"])
     assert not any(k.startswith("supp_backbone.") for k in raw["optimizer"]["momentum_buffer"])
-    eng, it = checkpoint.resume_training(p, lambda s: _FakeEngine(s, False), siamese_backbone=False)
+    eng, it = checkpoint.resume_training(p, lambda s: FakeEngine(s, siamese_backbone=False), siamese_backbone=False)
     assert it == 20 and eng.opt_state["steps"] == 3 and list(eng.sd) == list(spec.hot_path_shapes(False))
     assert all(torch.equal(eng.sd[k], sd[k]) for k in sd)
-    eng, _ = checkpoint.resume_training(p, lambda s: _FakeEngine(s, False))        # mode taken from the file
+    eng, _ = checkpoint.resume_training(p, lambda s: FakeEngine(s, siamese_backbone=False))        # mode taken from the file
     # a mode mismatch is refused, never silently re-tied / untied
     with pytest.raises(ValueError, match="untie"):
-        checkpoint.resume_training(p, lambda s: _FakeEngine(s, True), siamese_backbone=True)
+        checkpoint.resume_training(p, lambda s: FakeEngine(s, siamese_backbone=True), siamese_backbone=True)
     with pytest.raises(ValueError, match="shared-backbone"):
-        checkpoint.resume_training(p, lambda s: _FakeEngine(s, True))
+        checkpoint.resume_training(p, lambda s: FakeEngine(s, siamese_backbone=True))
     p2 = str(tmp_path / "model_siamese.pth")
-    checkpoint.save_training_checkpoint(p2, _FakeEngine(_sd(spec.hot_path_shapes(True)), True), 5)
+    checkpoint.save_training_checkpoint(p2, FakeEngine(_sd(spec.hot_path_shapes(True)), siamese_backbone=True), 5)
     assert torch.load(p2, map_location="cpu", weights_only=False)["siamese_backbone"] is True
     with pytest.raises(ValueError, match="tie"):
-        checkpoint.resume_training(p2, lambda s: _FakeEngine(s, False), siamese_backbone=False)
+        checkpoint.resume_training(p2, lambda s: FakeEngine(s, siamese_backbone=False), siamese_backbone=False)
     # an older training checkpoint without the recorded mode: the key set decides
     raw2 = torch.load(p2, map_location="cpu", weights_only=False)
     del raw2["siamese_backbone"]
     torch.save(raw2, p2)
     with pytest.raises(ValueError):
-        checkpoint.resume_training(p2, lambda s: _FakeEngine(s, False), siamese_backbone=False)
-    eng, it = checkpoint.resume_training(p2, lambda s: _FakeEngine(s, True))
+        checkpoint.resume_training(p2, lambda s: FakeEngine(s, siamese_backbone=False), siamese_backbone=False)
+    eng, it = checkpoint.resume_training(p2, lambda s: FakeEngine(s, siamese_backbone=True))
     assert it == 5 and any(k.startswith("supp_backbone.") for k in eng.sd)
 
 
