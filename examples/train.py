@@ -9,6 +9,9 @@ RyanXLi/OneshotDet drive it (both stages, SGD with the reference's parameter gro
                              [--box-cls-loss ce_loss|focal_loss|mse_loss|l1_loss|cxe_loss]   # the second stage's classification loss
                              [--soft-labeling] [--soft-labeling-func discrete|linear|transLinear|trans4thLinear]   # IoU soft labels
                                                         # (FEW_SHOT.SOFT_LABELING): mse_loss is held against them, l1_loss / cxe_loss need them
+                             [--lr-steps 60000,90000,120000] [--lr-gamma 0.1] [--warmup-iters 100] [--warmup-factor 0.3333]
+                             [--warmup-method constant|linear]      # the learning-rate schedule (SOLVER.STEPS, GAMMA, WARMUP_*);
+                                                        # default: the yaml of record's.  --constant-lr: no schedule, 0.0005 throughout
     python examples/train.py --no-center-sample --loc-loss-type iou ...    # the loss of the reference's defaults (defaults.py:309-311)
     python examples/train.py --shared-backbone --no-supp-roialign ...      # the 0930 model (configs/fcos/0930fixed_thres.yaml)
     python -m torch.distributed.run --nproc-per-node 8 --master-addr 127.0.0.1 examples/train.py ...      # one rank per GPU
@@ -20,9 +23,11 @@ RyanXLi/OneshotDet drive it (both stages, SGD with the reference's parameter gro
     fused device kernels), boxes follow their image; `transforms.collate(..., stem_dtype)` = BatchCollator straight into the
     stem conv's input format;
   * step: `TrainEngine.train_step` = forward + FCOS loss + second-stage loss + backward + (N > 1: bucketed RCCL all-reduce
-    behind the backward pass) + SGD + weight repack;
-  * checkpoints: `checkpoint.save_training_checkpoint` writes the reference's `{"model", "optimizer", "iteration"}` format
-    (reference parameter names, momentum included); `--resume` continues from `last_checkpoint`.
+    behind the backward pass) + SGD + weight repack, at the rate of `solver.LRSchedule` (= WarmupMultiStepLR, tools/train_net.py:80-81)
+    for the step's iteration;
+  * checkpoints: `checkpoint.save_training_checkpoint` writes the reference's `{"model", "optimizer", "scheduler", "iteration"}`
+    format (reference parameter names, momentum included); `--resume` continues from `last_checkpoint`, the schedule at the
+    restored iteration.
 """
 import argparse
 import os
@@ -32,7 +37,7 @@ import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from oneshotdet_amd import checkpoint, dataset, spec, synth, train, transforms as T  # noqa: E402
+from oneshotdet_amd import checkpoint, dataset, solver, spec, synth, train, transforms as T  # noqa: E402
 
 
 def synthetic_coco(rng, n_images=24, n_categories=3):
@@ -79,7 +84,18 @@ def main():
                          "loss_cls_suppress (FEW_SHOT.NEG_SUPPORT; 'ce_loss', one shot, no --linear-fusion).  The reference ships no "
                          "rule for choosing the negative support (its dataset's negative category is always -1); this example's own "
                          "rule: sample i's negative support is the support crop of sample (i + 1) mod batch")
+    rec = solver.LRSchedule.of_record()
+    ap.add_argument("--lr-steps", default=",".join(str(m) for m in rec.milestones), help="iterations at which the rate is multiplied by "
+                    "--lr-gamma, comma separated (SOLVER.STEPS); '' = none")
+    ap.add_argument("--lr-gamma", type=float, default=rec.gamma, help="SOLVER.GAMMA")
+    ap.add_argument("--warmup-iters", type=int, default=rec.warmup_iters, help="SOLVER.WARMUP_ITERS")
+    ap.add_argument("--warmup-factor", type=float, default=rec.warmup_factor, help="SOLVER.WARMUP_FACTOR")
+    ap.add_argument("--warmup-method", default=rec.warmup_method, choices=["constant", "linear"], help="SOLVER.WARMUP_METHOD")
+    ap.add_argument("--constant-lr", action="store_true", help="no schedule: the base rate from the first step to the last")
     args = ap.parse_args()
+    schedule = None if args.constant_lr else solver.LRSchedule(
+        rec.base_lr, tuple(int(m) for m in args.lr_steps.split(",") if m.strip()), args.lr_gamma, args.warmup_factor, args.warmup_iters,
+        args.warmup_method)
     # the model's options (spec.MODEL_OPTIONS), once: for the engine and, on --resume, as what the checkpoint is expected to hold
     options = dict(siamese_backbone=not args.shared_backbone, supp_roialign=not args.no_supp_roialign,
                    center_sample=not args.no_center_sample, loc_loss_type=args.loc_loss_type, box_cls_loss=args.box_cls_loss,
@@ -94,7 +110,7 @@ def main():
         **{name: options[name] for name in spec.SHAPE_OPTIONS})
 
     def make_engine(sd):
-        return train.TrainEngine(sd, dtype=dtype, lr=0.0005, second_stage=not args.first_stage_only, **options)
+        return train.TrainEngine(sd, dtype=dtype, lr=rec.base_lr, second_stage=not args.first_stage_only, lr_schedule=schedule, **options)
     start = 0
     last = os.path.join(args.out, "last_checkpoint")
     if args.resume and os.path.exists(last):
@@ -144,8 +160,8 @@ def main():
             extra = "" if eng.box_losses is None else "  loss_classifier %.4f  loss_box_reg %.4f" % tuple(eng.box_losses[:2].float().cpu())
             if eng.box_suppress_loss is not None:
                 extra += "  loss_cls_suppress %.4f" % float(eng.box_suppress_loss[0])
-            print("iter %4d  loss_cls %.4f  loss_reg %.4f  loss_centerness %.4f  (%d positives)%s"
-                  % (it, l[0], l[1], l[2], int(l[3]), extra))
+            print("iter %4d  lr: %.6f  loss_cls %.4f  loss_reg %.4f  loss_centerness %.4f  (%d positives)%s"      # trainer.py:114,125
+                  % (it, eng.lr, l[0], l[1], l[2], int(l[3]), extra))
         if rank == 0 and ((it + 1) % args.checkpoint_period == 0 or it + 1 == args.iters):
             path = os.path.join(args.out, "model_%07d.pth" % (it + 1))
             checkpoint.save_training_checkpoint(path, eng, it + 1)

@@ -149,6 +149,14 @@ SIGNATURES_NEG_SUPPORT = {
     "osd_box_loss_neg_support": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _f, _f, _f, _f, _p, _p, _p, _i, _i, _p]),
 }
 
+# include/oneshotdet_hip_solver.h: the optimiser update with its rate in device memory (a captured update under a learning-rate
+# schedule), a fifth table
+SIGNATURES_SOLVER = {
+    "osd_solver_set": (_i, [_p, _f, _i, _p]),
+    "osd_sgd_momentum_multi_dev": (_i, [_p, _p, _i, _p, _p, _p, _p, _f, _p]),
+    "osd_sgd_momentum_pack_multi_dev": (_i, [_p, _p, _i, _p, _p, _p, _p, _p, _i, _p, _f, _i, _p]),
+}
+
 _lib = None
 
 
@@ -168,7 +176,7 @@ def load():
     import torch  # noqa: F401  (loads libamdhip64 first)
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_BOX_MODES.items()) + list(SIGNATURES_SOFT_LABELS.items())
-                              + list(SIGNATURES_NEG_SUPPORT.items())):
+                              + list(SIGNATURES_NEG_SUPPORT.items()) + list(SIGNATURES_SOLVER.items())):
         fn = getattr(lib, name)   # AttributeError if the symbol is missing
         fn.restype = res
         fn.argtypes = args

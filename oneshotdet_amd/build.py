@@ -30,7 +30,7 @@ def build_library(force=False, verbose=True):
     objdir = os.path.join(LIBDIR, "obj" + ("_" + TAG if TAG else ""))
     os.makedirs(objdir, exist_ok=True)
     # every header under csrc/ is a dependency of every object (a handful of small files: a finer map is not worth a stale build)
-    headers = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join(os.path.dirname(HERE), "include", h) for h in ("oneshotdet_hip.h", "oneshotdet_hip_box_modes.h", "oneshotdet_hip_soft_labels.h", "oneshotdet_hip_neg_support.h")]
+    headers = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join(os.path.dirname(HERE), "include", h) for h in ("oneshotdet_hip.h", "oneshotdet_hip_box_modes.h", "oneshotdet_hip_soft_labels.h", "oneshotdet_hip_neg_support.h", "oneshotdet_hip_solver.h")]
     # objects of sources that are no longer built (retired kernels) do not stay behind: nothing links them, but they travel with
     # the snapshot and read as live code
     keep = set(src.replace(".hip", ".o") for src in SOURCES)

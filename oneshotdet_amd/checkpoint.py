@@ -139,9 +139,15 @@ def engine_options(engine):
 def save_training_checkpoint(path, engine, iteration, tag_last=True):
     """utils/checkpoint.py:33-50 as the trainer calls it (engine/trainer.py:111-119): model + optimizer + iteration.
     `optimizer` holds TrainEngine.optimizer_state_dict() (momentum buffers under reference names, steps taken, lr).  One more field
-    per row of spec.MODEL_OPTIONS: the options the engine trained with, most of which leave no other trace in the file."""
-    return save_checkpoint(path, engine.state_dict(), tag_last=tag_last, optimizer=engine.optimizer_state_dict(),
-                           iteration=int(iteration), **engine_options(engine))
+    per row of spec.MODEL_OPTIONS: the options the engine trained with, most of which leave no other trace in the file.  An engine
+    with a learning-rate schedule also writes the reference's `scheduler` field (checkpoint.py:44-45): solver.LRSchedule.state_dict()
+    under the reference scheduler's attribute names, last_epoch = the engine's update count."""
+    extras = OrderedDict(optimizer=engine.optimizer_state_dict(), iteration=int(iteration))
+    schedule = getattr(engine, "lr_schedule", None)
+    if schedule is not None:
+        extras["scheduler"] = schedule.state_dict(last_epoch=engine.iteration)
+    extras.update(engine_options(engine))
+    return save_checkpoint(path, engine.state_dict(), tag_last=tag_last, **extras)
 
 
 def _file_options(data):
@@ -168,7 +174,12 @@ def resume_training(path, make_engine, siamese_backbone=None, supp_roialign=None
     every row of spec.MODEL_OPTIONS the file's value is its record (a file written before the option existed: the row's default),
     and the keyword is what the caller expects (None: whatever the file holds).  An expectation that differs from the file is
     refused before make_engine is called, an engine that make_engine built otherwise after it: ValueError naming the file, the
-    option and both values.  The table's groups are looked at from the last to the first, each by its spec.OPTION_RULES."""
+    option and both values.  The table's groups are looked at from the last to the first, each by its spec.OPTION_RULES.
+    The learning-rate schedule is solver state, not a model option, and has no keyword: a file with a `scheduler` field and an engine
+    with lr_schedule must agree in every field but last_epoch (ValueError naming the field and both values); a file with one and an
+    engine without continue at the constant rate of the optimiser state; an engine with one continues it at the restored update count,
+    whatever the file holds.  (The reference's loader has its scheduler restore commented out, utils/checkpoint.py:68-70, so a
+    resumed reference run starts its warmup again; here the rate is a function of the restored count, on purpose.)"""
     expected = spec.options_in(locals())
     data = _read(path)
     record, trained = _file_options(data), OrderedDict()
@@ -185,6 +196,11 @@ def resume_training(path, make_engine, siamese_backbone=None, supp_roialign=None
         got = tuple(built[name] for name in spec.OPTION_GROUPS[group])
         if spec.OPTION_RULES[group].differs(values, got):
             raise ValueError("%s but make_engine built an engine with %s" % (_trained_with(path, group, values), spec.describe_group(group, got)))
+    schedule, recorded = getattr(eng, "lr_schedule", None), extras.get("scheduler")
+    if schedule is not None and isinstance(recorded, dict):
+        for field, mine, theirs in schedule.differences(recorded):
+            raise ValueError("%s was trained with the learning-rate schedule's %s = %r but make_engine built an engine whose schedule "
+                             "has %s = %r" % (path, field, theirs, field, mine))
     if "optimizer" in extras and isinstance(extras["optimizer"], dict) and "momentum_buffer" in extras["optimizer"]:
         eng.load_optimizer_state_dict(extras["optimizer"])
     return eng, int(extras.get("iteration", 0))

@@ -222,9 +222,19 @@ __device__ __forceinline__ float sgd_update(float w, float g, float b, float wd,
   return __builtin_fmaf(-step, m, w);
 }
 
-__global__ void __launch_bounds__(256) sgd_multi_kernel(const SgdEntry* __restrict__ table, const int* __restrict__ block_entry,
-                                                        float* __restrict__ p, const float* __restrict__ g,
-                                                        float* __restrict__ buf, float lr, float momentum, int first) {
+// The solver block of include/oneshotdet_hip_solver.h: the rate and the first-step flag in device memory, for an update inside a
+// captured graph.  The `_dev` kernels below load it once per workgroup (through a const __restrict__ kernel argument: a
+// wave-uniform load) and run the SAME body as the by-value kernels, which take the two values as kernel arguments.
+struct alignas(8) SolverBlock { float lr; int first_step; };
+static_assert(sizeof(SolverBlock) == 8, "solver block layout (oneshotdet_hip_solver.h)");
+
+__global__ void __launch_bounds__(64) solver_set_kernel(SolverBlock* __restrict__ block, float lr, int first_step) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) { block->lr = lr; block->first_step = first_step; }
+}
+
+__device__ __forceinline__ void sgd_multi_body(const SgdEntry* __restrict__ table, const int* __restrict__ block_entry,
+                                               float* __restrict__ p, const float* __restrict__ g,
+                                               float* __restrict__ buf, float lr, float momentum, int first) {
   const SgdEntry e = table[block_entry[blockIdx.x]];
   const float step = lr * e.lr_mult;
   const long long stride = (long long)e.n_blocks * blockDim.x;
@@ -254,6 +264,20 @@ __global__ void __launch_bounds__(256) sgd_multi_kernel(const SgdEntry* __restri
   }
 }
 
+__global__ void __launch_bounds__(256) sgd_multi_kernel(const SgdEntry* __restrict__ table, const int* __restrict__ block_entry,
+                                                        float* __restrict__ p, const float* __restrict__ g,
+                                                        float* __restrict__ buf, float lr, float momentum, int first) {
+  sgd_multi_body(table, block_entry, p, g, buf, lr, momentum, first);
+}
+
+__global__ void __launch_bounds__(256) sgd_multi_dev_kernel(const SgdEntry* __restrict__ table, const int* __restrict__ block_entry,
+                                                            float* __restrict__ p, const float* __restrict__ g,
+                                                            float* __restrict__ buf, const SolverBlock* __restrict__ solver,
+                                                            float momentum) {
+  const SolverBlock s = *solver;
+  sgd_multi_body(table, block_entry, p, g, buf, s.lr, momentum, s.first_step);
+}
+
 // ---- the same update that ALSO writes the forward-form packed weights of the conv tensors it updates (round 4): the repack
 // of the forward form is a scaled, rounded, K-padded copy in the masters' own [cout][R][S][cin] order, so the thread that holds
 // the four updated fp32 values stores them again as `T`, times the folded FrozenBN scale — the packed buffer's padding rows /
@@ -272,10 +296,10 @@ struct SgdPackEntry {
 };
 
 template <typename T>
-__global__ void __launch_bounds__(256) sgd_pack_multi_kernel(const SgdPackEntry* __restrict__ table, const int* __restrict__ block_entry,
-                                                             float* __restrict__ p, float* __restrict__ g, float* __restrict__ buf,
-                                                             const float* __restrict__ scales, T* __restrict__ packed, float lr,
-                                                             float momentum, int first, int zero_grads) {
+__device__ __forceinline__ void sgd_pack_multi_body(const SgdPackEntry* __restrict__ table, const int* __restrict__ block_entry,
+                                                    float* __restrict__ p, float* __restrict__ g, float* __restrict__ buf,
+                                                    const float* __restrict__ scales, T* __restrict__ packed, float lr,
+                                                    float momentum, int first, int zero_grads) {
   // zero_grads: the gradient is CONSUMED — zeros are stored behind the read, so the next step's weight-gradient kernels (which
   // accumulate atomically) find a clean buffer without a 236 MB memset on the critical path of the next forward pass
   const SgdPackEntry e = table[block_entry[blockIdx.x]];
@@ -335,6 +359,23 @@ __global__ void __launch_bounds__(256) sgd_pack_multi_kernel(const SgdPackEntry*
       packed[e.dst_off + ((size_t)co * e.rs + tap) * e.kpad + ci] = from_f32<T>(o * (sc ? sc[co] : 1.f));
     }
   }
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256) sgd_pack_multi_kernel(const SgdPackEntry* __restrict__ table, const int* __restrict__ block_entry,
+                                                             float* __restrict__ p, float* __restrict__ g, float* __restrict__ buf,
+                                                             const float* __restrict__ scales, T* __restrict__ packed, float lr,
+                                                             float momentum, int first, int zero_grads) {
+  sgd_pack_multi_body<T>(table, block_entry, p, g, buf, scales, packed, lr, momentum, first, zero_grads);
+}
+
+template <typename T>
+__global__ void __launch_bounds__(256) sgd_pack_multi_dev_kernel(const SgdPackEntry* __restrict__ table, const int* __restrict__ block_entry,
+                                                                 float* __restrict__ p, float* __restrict__ g, float* __restrict__ buf,
+                                                                 const float* __restrict__ scales, T* __restrict__ packed,
+                                                                 const SolverBlock* __restrict__ solver, float momentum, int zero_grads) {
+  const SolverBlock s = *solver;
+  sgd_pack_multi_body<T>(table, block_entry, p, g, buf, scales, packed, s.lr, momentum, s.first_step, zero_grads);
 }
 
 // packed fp32 weight gradient [cout][R][S][cin] -> OIHW, times the folded FrozenBN scale (d/dw of conv(x, w*scale))
@@ -703,6 +744,44 @@ extern "C" int osd_sgd_momentum_pack_multi(const void* table, const int32_t* blo
       hipLaunchKernelGGL(sgd_pack_multi_kernel<__bf16>, dim3(n_blocks), dim3(256), 0, OSD_STREAM(stream), (const SgdPackEntry*)table, block_entry,
                          params, grads, momentum_buf, scales, (__bf16*)packed, lr, momentum, first_step, zero_grads));
   return osd_check_launch("sgd_pack_multi");
+}
+
+// include/oneshotdet_hip_solver.h: the rate and the first-step flag from the 8-byte solver block
+static int solver_block_ok(const void* block, const char* who) {
+  if (!block) return osd_fail(OSD_ERR_INVALID_ARG, "%s: null solver block", who);
+  if (reinterpret_cast<uintptr_t>(block) & 7) return osd_fail(OSD_ERR_INVALID_ARG, "%s: the solver block %p is not 8-byte aligned", who, block);
+  return OSD_OK;
+}
+
+extern "C" int osd_solver_set(void* block, float lr, int first_step, void* stream) {
+  if (const int rc = solver_block_ok(block, "solver_set")) return rc;
+  hipLaunchKernelGGL(solver_set_kernel, dim3(1), dim3(64), 0, OSD_STREAM(stream), (SolverBlock*)block, lr, first_step);
+  return osd_check_launch("solver_set");
+}
+
+extern "C" int osd_sgd_momentum_multi_dev(const void* table, const int32_t* block_entry, int n_blocks, float* params,
+                                          const float* grads, float* momentum_buf, const void* solver_block, float momentum,
+                                          void* stream) {
+  if (!table || !block_entry || !params || !grads || !momentum_buf) return osd_fail(OSD_ERR_INVALID_ARG, "sgd_dev: null argument");
+  if (const int rc = solver_block_ok(solver_block, "sgd_dev")) return rc;
+  if (n_blocks <= 0) return OSD_OK;
+  hipLaunchKernelGGL(sgd_multi_dev_kernel, dim3(n_blocks), dim3(256), 0, OSD_STREAM(stream), (const SgdEntry*)table, block_entry,
+                     params, grads, momentum_buf, (const SolverBlock*)solver_block, momentum);
+  return osd_check_launch("sgd_multi_dev");
+}
+
+extern "C" int osd_sgd_momentum_pack_multi_dev(const void* table, const int32_t* block_entry, int n_blocks, float* params,
+                                               float* grads, float* momentum_buf, const float* scales, void* packed, int dtype,
+                                               const void* solver_block, float momentum, int zero_grads, void* stream) {
+  if (!table || !block_entry || !params || !grads || !momentum_buf || !packed) return osd_fail(OSD_ERR_INVALID_ARG, "sgd_pack_dev: null argument");
+  if (const int rc = solver_block_ok(solver_block, "sgd_pack_dev")) return rc;
+  if (n_blocks <= 0) return OSD_OK;
+  OSD_DISPATCH_DTYPE(dtype,
+      hipLaunchKernelGGL(sgd_pack_multi_dev_kernel<float>, dim3(n_blocks), dim3(256), 0, OSD_STREAM(stream), (const SgdPackEntry*)table, block_entry,
+                         params, grads, momentum_buf, scales, (float*)packed, (const SolverBlock*)solver_block, momentum, zero_grads),
+      hipLaunchKernelGGL(sgd_pack_multi_dev_kernel<__bf16>, dim3(n_blocks), dim3(256), 0, OSD_STREAM(stream), (const SgdPackEntry*)table, block_entry,
+                         params, grads, momentum_buf, scales, (__bf16*)packed, (const SolverBlock*)solver_block, momentum, zero_grads));
+  return osd_check_launch("sgd_pack_multi_dev");
 }
 
 extern "C" int osd_unpack_wgrad(const float* dw_packed, const float* scale, float* grad_oihw, int cout, int cin, int r, int s,

@@ -1489,3 +1489,30 @@ def proposals_sort_nms(keys, boxes, max_count, levels, topn, thresh, max_keep, c
               int(cuda_semantics), max_keep, int(head_hint), _p(workspace), _p(ob), _p(os_), _p(oc), _p(depth_out),
               _stream())
     return ob, os_, oc
+
+
+# ---------------------------------------------------------------------------------------------------- solver (oneshotdet_hip_solver.h)
+def solver_block(device):
+    """The 8-byte solver block { float lr; int32 first_step; } the `_dev` update entries read (8-byte aligned: one int64)."""
+    return torch.zeros((1,), device=device, dtype=torch.int64)
+
+
+def solver_set(block, lr, first_step):
+    """osd_solver_set: write (lr, first_step) into the solver block on the current stream — between graph launches, never inside a
+    capture."""
+    _chk_dev(block)
+    _lib.call("osd_solver_set", _ptr(block), float(lr), int(bool(first_step)), _stream())
+
+
+def sgd_momentum_multi_dev(table, block_entry, n_blocks, params, grads, momentum_buf, solver, momentum):
+    """osd_sgd_momentum_multi with the rate and the first-step flag read from the solver block (osd_sgd_momentum_multi_dev)."""
+    _lib.call("osd_sgd_momentum_multi_dev", _ptr(table), _ptr(block_entry), int(n_blocks), _ptr(params), _ptr(grads),
+              _ptr(momentum_buf), _ptr(solver), float(momentum), _stream())
+
+
+def sgd_momentum_pack_multi_dev(table, block_entry, n_blocks, params, grads, momentum_buf, scales, packed, solver, momentum,
+                                zero_grads):
+    """osd_sgd_momentum_pack_multi with the rate and the first-step flag read from the solver block
+    (osd_sgd_momentum_pack_multi_dev); `packed`'s dtype is the packed weights'."""
+    _lib.call("osd_sgd_momentum_pack_multi_dev", _ptr(table), _ptr(block_entry), int(n_blocks), _ptr(params), _ptr(grads),
+              _ptr(momentum_buf), _ptr(scales), _ptr(packed), _dt(packed), _ptr(solver), float(momentum), int(zero_grads), _stream())

@@ -113,7 +113,7 @@ class TrainEngine(ForwardPass, BackwardPass, SecondStage, Update, State):
                  process_group=None, wgrad_side_stream=True, optimizer="fused", second_stage=False, ordered_wgrad=None,
                  exchange_single_rank=False, grad_wire_dtype=None, siamese_backbone=True, supp_roialign=True,
                  center_sample=True, loc_loss_type="giou", box_cls_loss="ce_loss", soft_labeling=False, soft_labeling_func="linear",
-                 linear_fusion=False, neg_support=False):
+                 linear_fusion=False, neg_support=False, lr_schedule=None):
         # spec.MODEL_OPTIONS: ValueError by name before anything is built; every row becomes an attribute
         vars(self).update(spec.check_options("the TrainEngine", second_stage, **spec.options_in(locals()))._asdict())
         if not torch.cuda.is_available():
@@ -250,10 +250,15 @@ class TrainEngine(ForwardPass, BackwardPass, SecondStage, Update, State):
         biases = [c.b for c in self.convs.values() if c.trainable and c.has_bias] + \
                  [p for n, (p, _) in self.extra.items() if "bias" in n]
         self.lr, self.momentum, self.weight_decay = lr, momentum, weight_decay
+        # lr_schedule (solver.LRSchedule, or None: `lr` stays whatever it is set to): every step takes its rate from the schedule
+        # at the engine's own update count, so every rank derives the same rate and nothing is exchanged.  _solver: the 8-byte device
+        # block a captured update reads its rate from (capture()); _dev_update: the update launches being enqueued are captured ones
+        self.lr_schedule, self._solver, self._dev_update = lr_schedule, None, False
         self.opt = None
         if optimizer == "torch":     # the reference's optimiser object, kept for A/B tests of the fused kernel
             self.opt = torch.optim.SGD([{"params": weights, "lr": lr, "weight_decay": weight_decay},
                                         {"params": biases, "lr": 2 * lr, "weight_decay": 0.0}], lr=lr, momentum=momentum)
+            self._sgd = dict(tables={}, buf=None, steps=0)      # the update count only (`iteration`)
         else:
             self._build_sgd_table(weights, biases)
 
@@ -666,9 +671,24 @@ class TrainEngine(ForwardPass, BackwardPass, SecondStage, Update, State):
         they became final during backward (dist_utils.GradExchange); this waits for them."""
         self.exchange.finish()        # buckets not announced during backward (graph replay, single stream) go now
 
+    @property
+    def iteration(self):
+        """Updates applied so far: the index of the next one in the learning-rate schedule, and a checkpoint's `last_epoch`."""
+        return self._sgd["steps"]
+
+    def _scheduled_lr(self):
+        """With a schedule: `lr` of the update about to run (solver.LRSchedule.lr_at(iteration)); the torch optimiser's two
+        parameter groups follow (weights lr, biases 2 lr: solver/build.py:8-26).  Without one nothing happens."""
+        if self.lr_schedule is None:
+            return
+        self.lr = self.lr_schedule.lr_at(self.iteration)
+        if self.opt is not None:
+            self.opt.param_groups[0]["lr"], self.opt.param_groups[1]["lr"] = self.lr, 2 * self.lr
+
     def train_step(self, images, queries, gt_boxes, gt_count, neg_queries=None):
         """forward + loss + backward + gradient averaging + SGD + repack.  With the fused optimiser each bucket's exchange,
         update and repack run on a side stream as soon as the bucket is final, beside the rest of the backward pass."""
+        self._scheduled_lr()           # here: the overlapped bucket updates start inside the backward pass
         self._fuse_update = self.opt is None and self._overlap
         # defer_join: do not make the main stream wait for the step's tail (the last stage's weight gradients, their
         # exchange, update and repack): the next step's frozen layers (stem, layer1) run beside it.  Every bucket's update
@@ -690,11 +710,19 @@ class TrainEngine(ForwardPass, BackwardPass, SecondStage, Update, State):
 
     def capture(self, images, queries, gt_boxes, gt_count, warmup=2):
         """Capture the training step into hipGraphs (forward+loss+backward as one graph, SGD + repack as another, with the
-        RCCL all-reduce between them launched normally): ~1500 launches per step become two graph launches.  The learning
-        rate is baked in at capture time; call capture() again after changing it."""
+        RCCL all-reduce between them launched normally): ~1500 launches per step become two graph launches.  Without a
+        schedule the learning rate is baked in at capture time; call capture() again after changing it.  With lr_schedule the
+        captured update reads its rate and its first-step flag from an 8-byte device block (osd_sgd_momentum_*_dev,
+        include/oneshotdet_hip_solver.h), which replay_step() rewrites before every replay (osd_solver_set, one small launch
+        outside the graphs): the replayed steps follow the schedule, and `lr` assigned by hand after the schedule has been taken
+        away is honoured too.  The update count (`iteration`) after capture() counts the warm-up steps, which are real training
+        steps, and not the captured update, which has not run."""
         if self.neg_support:
             raise ValueError("capture() does not take the negative supports of neg_support=True (FEW_SHOT.NEG_SUPPORT) yet: run "
                              "train_step(..., neg_queries=) eagerly")
+        if self.lr_schedule is not None and self.opt is not None:
+            raise ValueError("capture() with lr_schedule needs the fused optimiser: a captured torch.optim.SGD keeps the rates it was "
+                             "captured with")
         # static copies of the inputs; a padded batch (layers.ImageList / ops.PackedImages) keeps its per-image sizes, which
         # are baked into the captured graph together with the batch shape
         self._static = [_static_clone(t) for t in (images, queries, gt_boxes, gt_count)]
@@ -716,18 +744,33 @@ class TrainEngine(ForwardPass, BackwardPass, SecondStage, Update, State):
         self._g_fb = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self._g_fb):
             self._static_losses = self.forward_backward(*self._static)
+        # with a schedule the captured update reads the block replay_step() writes (zero until then)
+        self._solver = ops.solver_block(self.device) if self.lr_schedule is not None else None
+        steps = self._sgd["steps"]
         self._g_opt = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self._g_opt):
-            self.optimizer_step()
+        self._dev_update = self._solver is not None
+        try:
+            with torch.cuda.graph(self._g_opt):
+                self.optimizer_step()
+        finally:
+            self._dev_update = False
+        self._sgd["steps"] = steps        # the captured update has not run
         return self
 
     def replay_step(self, images=None, queries=None, gt_boxes=None, gt_count=None):
         for dst, src in zip(self._static, (images, queries, gt_boxes, gt_count)):
             if src is not None:
                 _static_copy(dst, src)
+        if self.lr_schedule is not None and self._solver is None:
+            raise ValueError("replay_step: the engine was captured without a learning-rate schedule, its rate is part of the graph; "
+                             "call capture() again")
+        self._scheduled_lr()
         self._g_fb.replay()
         self.reduce_gradients()
+        if self._solver is not None:
+            ops.solver_set(self._solver, self.lr, self.iteration == 0)
         self._g_opt.replay()
+        self._sgd["steps"] += 1
         # what the host flags say after a replay is what they said at capture time; be conservative for whatever eager call
         # follows: it zeroes the buffer itself (one memset), and the next replay zeroes inside its graph
         self._grads_clean, self._zeroed, self._updated = False, set(), set()

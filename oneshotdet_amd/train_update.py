@@ -146,13 +146,22 @@ class Update(object):
         sg = self._sgd
         tb = sg["tables"].get(name)
         fused = tb is not None and tb["fused"]
-        if fused:
+        if fused and self._dev_update:      # a captured update under a schedule: rate and first-step flag from the device block
+            pk = self._pack[0]["flat"]
+            ops.sgd_momentum_pack_multi_dev(tb["table"], tb["blocks"], tb["n"], self.flat_w, self.flat_g, sg["buf"], self._flat_scale,
+                                            pk, self._solver, self.momentum, self.consume_grads)
+            if self.consume_grads:
+                self._zeroed.add(name)
+        elif fused:
             pk = self._pack[0]["flat"]
             ops._lib.call("osd_sgd_momentum_pack_multi", ops._ptr(tb["table"]), ops._ptr(tb["blocks"]), tb["n"],
                           ops._ptr(self.flat_w), ops._ptr(self.flat_g), ops._ptr(sg["buf"]), ops._ptr(self._flat_scale), ops._ptr(pk),
                           ops._dt(pk), float(self.lr), float(self.momentum), int(sg["steps"] == 0), int(self.consume_grads), ops._stream())
             if self.consume_grads:
                 self._zeroed.add(name)
+        elif tb is not None and self._dev_update:
+            ops.sgd_momentum_multi_dev(tb["table"], tb["blocks"], tb["n"], self.flat_w, self.flat_g, sg["buf"], self._solver,
+                                       self.momentum)
         elif tb is not None:
             ops._lib.call("osd_sgd_momentum_multi", ops._ptr(tb["table"]), ops._ptr(tb["blocks"]), tb["n"],
                           ops._ptr(self.flat_w), ops._ptr(self.flat_g), ops._ptr(sg["buf"]), float(self.lr),
@@ -162,9 +171,11 @@ class Update(object):
 
     def optimizer_step(self):
         """Apply the update to every bucket train_step has not already updated behind the backward pass."""
+        self._scheduled_lr()
         if self.opt is not None:
             self.opt.step()
             self.repack()
+            self._sgd["steps"] += 1
             return
         if self._overlap:              # (never inside a captured graph: capture() turns the overlap off)
             main = streams.current()
