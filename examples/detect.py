@@ -3,6 +3,7 @@
     python examples/detect.py [--checkpoint model_0040000.pth | --c2 R-50.pkl] [--dtype bf16|f32] [--second-stage]
                               [--shared-backbone] [--no-supp-roialign] [--box-cls-loss ce_loss|focal_loss|mse_loss|l1_loss|cxe_loss]
                               [--soft-labeling]       # the model was trained with FEW_SHOT.SOFT_LABELING (needed for l1_loss / cxe_loss)
+                              [--classes K]           # the class sweep: K categories per image in one pass, one merged BoxList per image
     python examples/detect.py --checkpoint model_0930.pth --shared-backbone --no-supp-roialign      # the 0930 model
 
   * weights: a reference `.pth` (utils/checkpoint.py format), a Detectron ResNet `.pkl` for the backbones, or — there is no
@@ -13,7 +14,9 @@
     with --shared-backbone, and nothing in a weights file says so (a training checkpoint of this build records it);
   * inputs: lists of CHW BGR-minus-mean images of different sizes for targets and queries; `to_image_list` pads them to
     a common /32 size and keeps the true sizes (data/collate_batch.py + structures/image_list.py of the reference);
-  * output: one BoxList per target image (boxes, scores, labels = the query's class id), like `GeneralizedRCNN.forward`.
+  * output: one BoxList per target image (boxes, scores, labels = the query's class id), like `GeneralizedRCNN.forward`;
+  * --classes K: every image is asked about K categories at once (K supports per image, `target_ids` = K ids per image): the target
+    backbone runs once per image, and the BoxList of an image holds the detections of all K categories in descending score order.
 """
 import argparse
 import os
@@ -44,6 +47,9 @@ def main():
     ap.add_argument("--neg-support", action="store_true",
                     help="the model was trained with a negative support (FEW_SHOT.NEG_SUPPORT; 'ce_loss', no --linear-fusion): "
                          "validated, detection itself does not change")
+    ap.add_argument("--classes", type=int, default=1,
+                    help="K: ask every image about K categories in one pass (the class sweep, detect(..., classes=K)); the supports "
+                         "are synthetic here")
     args = ap.parse_args()
     siamese = not args.shared_backbone
     roialign = not args.no_supp_roialign
@@ -80,6 +86,21 @@ def main():
     images = layers.to_image_list(targets, size_divisible=spec.SIZE_DIVISIBILITY)
     images_supp = layers.to_image_list(queries, size_divisible=spec.SIZE_DIVISIBILITY)
     print("padded batch", tuple(images.tensors.shape), "true sizes", images.image_sizes)
+    if args.classes > 1:
+        # K supports per image, row b*K + k = category slot k of image b (synthetic: no two alike), and K class ids per image
+        K = args.classes
+        sizes = [(127, 127), (96, 160)]
+        supports = [torch.from_numpy(synth.make_images("ex.q%d.%d" % (b, k), 1, *sizes[(b + k) % 2])[0]) for b in range(2) for k in range(K)]
+        images_supp = layers.to_image_list(supports, size_divisible=spec.SIZE_DIVISIBILITY)
+        ids = [[1 + (17 * b + k) % 80 for k in range(K)] for b in range(2)]
+        results = det(images, images_supp, target_ids=ids)
+        torch.cuda.synchronize()
+        for i, bl in enumerate(results):
+            labels = bl.get_field("labels").cpu().tolist()
+            per_class = {c: labels.count(c) for c in ids[i]}
+            print("image %d: %s merged from %d categories, per category %s, top score %.3f (label %s)" % (
+                i, bl, K, per_class, float(bl.get_field("scores")[0]) if len(bl) else float("nan"), labels[0] if labels else "-"))
+        return
     results = det(images, images_supp, target_ids=[17, 3])
     torch.cuda.synchronize()
     for i, bl in enumerate(results):

@@ -157,6 +157,13 @@ SIGNATURES_SOLVER = {
     "osd_sgd_momentum_pack_multi_dev": (_i, [_p, _p, _i, _p, _p, _p, _p, _p, _i, _p, _f, _i, _p]),
 }
 
+# include/oneshotdet_hip_class_sweep.h: K category slots per target image in one pass (the class sweep), a sixth table
+SIGNATURES_CLASS_SWEEP = {
+    "osd_class_sweep_group": (_i, []),
+    "osd_correlate_levels_sweep": (_i, [_i, _p, _p, _p, _p, _i, _i, _i, _i, _p]),
+    "osd_roi_pool_levels_sweep": (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _i, _p]),
+}
+
 _lib = None
 
 
@@ -176,7 +183,8 @@ def load():
     import torch  # noqa: F401  (loads libamdhip64 first)
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_BOX_MODES.items()) + list(SIGNATURES_SOFT_LABELS.items())
-                              + list(SIGNATURES_NEG_SUPPORT.items()) + list(SIGNATURES_SOLVER.items())):
+                              + list(SIGNATURES_NEG_SUPPORT.items()) + list(SIGNATURES_SOLVER.items())
+                              + list(SIGNATURES_CLASS_SWEEP.items())):
         fn = getattr(lib, name)   # AttributeError if the symbol is missing
         fn.restype = res
         fn.argtypes = args

@@ -94,9 +94,12 @@ def run_query_roi(qfeats, q_size, dtype):
     return ops.roi_pool_levels(qfeats, spec.POOLER_SCALES, boxes, None, spec.BOX_POOL, spec.POOLER_SAMPLING_RATIO)
 
 
-def run_box_head(bw, feats, qfeats, q_size, boxes, counts, img_h, img_w, shots=1, cuda_nms=True, want_raw=False, img_hw=None):
+def run_box_head(bw, feats, qfeats, q_size, boxes, counts, img_h, img_w, shots=1, cuda_nms=True, want_raw=False, img_hw=None,
+                 classes=1):
     """feats / qfeats: NHWC P3..P7 of the target / query backbone; boxes [N,R,4], counts [N] = first-stage proposals.
-    Returns dict(boxes [N,K,4], scores [N,K] descending, counts [N]) (+ raw logits / deltas / pooled maps)."""
+    Returns dict(boxes [N,K,4], scores [N,K] descending, counts [N]) (+ raw logits / deltas / pooled maps).
+    classes = K (the class sweep): N = B*K rows of proposals (row b*K + k), feats has B images, qfeats B*K*shots, img_hw N rows; the
+    ROI pooling reads image row // K and everything after it is the per-pair head on N rows."""
     n, r, _ = boxes.shape
     dtype = feats[0].dtype
     check_shots(bw.box_cls_loss, shots)                                                # nothing has been launched yet
@@ -106,7 +109,8 @@ def run_box_head(bw, feats, qfeats, q_size, boxes, counts, img_h, img_w, shots=1
     # FEW_SHOT.LINEAR_FUSION (box_head.py:61-72,148): the head in front of fc6 is the split 3x3 conv, GroupNorm, LeakyReLU
     conv_q, conv_x, pad = (bw.aggreg_q, bw.aggreg_x, 1) if linear else (bw.conv0_q, bw.conv0_x, 0)
     q_half = ops.conv2d(q, conv_q, pad=pad)                                            # [N*S,7,7,512 | 128]  W_q q + b
-    x = ops.roi_pool_levels(feats, spec.POOLER_SCALES, boxes, counts, spec.BOX_POOL, spec.POOLER_SAMPLING_RATIO)
+    x = ops.roi_pool_levels(feats, spec.POOLER_SCALES, boxes, counts, spec.BOX_POOL, spec.POOLER_SAMPLING_RATIO,
+                            sets_per_image=classes)
     u0 = ops.conv2d(x, conv_x, pad=pad)                                                # [N*R,7,7,512 | 128]  W_x x, once for all shots
     preds = torch.empty((shots, n * r, bw.pred.cout_store), device=boxes.device, dtype=dtype)
     for s in range(shots):                                                             # box_head.py:122

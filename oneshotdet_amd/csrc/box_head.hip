@@ -6,6 +6,7 @@
 // All HBM-bound.  The convolutions / fully connected layers of the head run on the implicit-GEMM kernels.
 #include "osd_common.h"
 #include "../../include/oneshotdet_hip_box_modes.h"
+#include "../../include/oneshotdet_hip_class_sweep.h"
 
 namespace {
 
@@ -87,11 +88,13 @@ __device__ __forceinline__ int map_level(float x1, float y1, float x2, float y2,
 // (Tried: staging the ROI's pixel patch, one 64-channel slab per workgroup, in LDS before the taps - bit-identical, but
 // 5 % slower end to end, 996 vs 1045 images/s: the vector L1 already serves the repeated taps, and the staged version
 // pays a barrier, an LDS round trip and 4x the workgroups.)
+// `sets_per_image`: ROI set (boxes / counts row) j reads image j / sets_per_image of the level maps — 1 for the per-pair entry, the
+// class sweep's K for osd_roi_pool_levels_sweep (include/oneshotdet_hip_class_sweep.h); one body for both kernels.
 template <typename T>
-__global__ __launch_bounds__(256) void roi_pool_levels_kernel(PoolLevels lv, const float* __restrict__ boxes,
-                                                              const int32_t* __restrict__ counts, T* __restrict__ y, int c,
-                                                              int max_rois, int pool, int sampling, int y_stride,
-                                                              int32_t* __restrict__ level_out) {
+__device__ __forceinline__ void roi_pool_levels_body(const PoolLevels& lv, const float* __restrict__ boxes,
+                                                     const int32_t* __restrict__ counts, T* __restrict__ y, int c, int max_rois,
+                                                     int pool, int sampling, int y_stride, int32_t* __restrict__ level_out,
+                                                     int sets_per_image) {
   constexpr int E = Chunk<T>::E;
   const int roi = blockIdx.x;
   const int img = roi / max_rois, ri = roi % max_rois;
@@ -114,7 +117,7 @@ __global__ __launch_bounds__(256) void roi_pool_levels_kernel(PoolLevels lv, con
   if (level_out && threadIdx.x == 0) level_out[roi] = l;
   const int h = lv.h[l], w = lv.w[l];
   const float scale = lv.scale[l];
-  const T* x = reinterpret_cast<const T*>(lv.x[l]) + (size_t)img * h * w * c;
+  const T* x = reinterpret_cast<const T*>(lv.x[l]) + (size_t)(img / sets_per_image) * h * w * c;
   const float rsw = x1 * scale, rsh = y1 * scale, rew = x2 * scale, reh = y2 * scale;
   const float roi_w = fmaxf(rew - rsw, 1.f), roi_h = fmaxf(reh - rsh, 1.f);
   const float bin_h = roi_h / (float)pool, bin_w = roi_w / (float)pool;
@@ -194,6 +197,22 @@ __global__ __launch_bounds__(256) void roi_pool_levels_kernel(PoolLevels lv, con
     for (int e = 0; e < E; ++e) o.v[e] = acc[e] / count;
     o.store(yr + (size_t)cell * y_stride + ch);
   }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void roi_pool_levels_kernel(PoolLevels lv, const float* __restrict__ boxes,
+                                                              const int32_t* __restrict__ counts, T* __restrict__ y, int c,
+                                                              int max_rois, int pool, int sampling, int y_stride,
+                                                              int32_t* __restrict__ level_out) {
+  roi_pool_levels_body<T>(lv, boxes, counts, y, c, max_rois, pool, sampling, y_stride, level_out, 1);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void roi_pool_levels_sweep_kernel(PoolLevels lv, const float* __restrict__ boxes,
+                                                                    const int32_t* __restrict__ counts, T* __restrict__ y, int c,
+                                                                    int max_rois, int pool, int sampling, int y_stride,
+                                                                    int32_t* __restrict__ level_out, int sets_per_image) {
+  roi_pool_levels_body<T>(lv, boxes, counts, y, c, max_rois, pool, sampling, y_stride, level_out, sets_per_image);
 }
 
 // GroupNorm(groups, C) + LeakyReLU(slope) of one ROI map [hw][C] per workgroup (hw = 49): the whole sample sits in
@@ -422,6 +441,36 @@ extern "C" int osd_roi_pool_levels(int n_levels, const void* const* xs, const in
   else
     return osd_fail(OSD_ERR_INVALID_ARG, "bad dtype %d", dtype);
   return osd_check_launch("roi_pool_levels");
+}
+
+// include/oneshotdet_hip_class_sweep.h
+extern "C" int osd_roi_pool_levels_sweep(int n_levels, const void* const* xs, const int32_t* hs, const int32_t* ws,
+                                         const float* scales, const float* boxes, const int32_t* counts, void* y, int n_sets,
+                                         int sets_per_image, int c, int max_rois, int pool, int sampling_ratio, int y_stride,
+                                         int32_t* level_out, int dtype, void* stream) {
+  if (n_levels < 1 || n_levels > OSD_MAX_ROI_LEVELS || !xs || !hs || !ws || !scales || !boxes || !y || n_sets < 0 || max_rois < 0)
+    return osd_fail(OSD_ERR_INVALID_ARG, "roi_pool_levels_sweep: bad args");
+  if (sets_per_image < 1 || n_sets % sets_per_image != 0)
+    return osd_fail(OSD_ERR_INVALID_ARG, "roi_pool_levels_sweep: %d ROI sets are no multiple of %d sets per image", n_sets,
+                    sets_per_image);
+  const int e = dtype == OSD_BF16 ? 8 : 4;
+  if (c % e != 0 || y_stride < c || y_stride % e != 0 || pool < 1)
+    return osd_fail(OSD_ERR_INVALID_ARG, "roi_pool_levels_sweep: channels %d / stride %d must be multiples of %d", c, y_stride, e);
+  if (dtype != OSD_F32 && dtype != OSD_BF16) return osd_fail(OSD_ERR_INVALID_ARG, "bad dtype %d", dtype);
+  for (int l = 0; l < n_levels; ++l)
+    if (!xs[l]) return osd_fail(OSD_ERR_INVALID_ARG, "roi_pool_levels_sweep: null level %d", l);
+  if ((long long)n_sets * max_rois > 0x7fffffffLL) return osd_fail(OSD_ERR_INVALID_ARG, "roi_pool_levels_sweep: too many ROIs");
+  if (n_sets * max_rois == 0) return OSD_OK;
+  PoolLevels lv;
+  lv.n_levels = n_levels;
+  for (int l = 0; l < n_levels; ++l) { lv.x[l] = xs[l]; lv.h[l] = hs[l]; lv.w[l] = ws[l]; lv.scale[l] = scales[l]; }
+  if (dtype == OSD_F32)
+    hipLaunchKernelGGL(roi_pool_levels_sweep_kernel<float>, dim3(n_sets * max_rois), dim3(256), 0, OSD_STREAM(stream), lv, boxes,
+                       counts, (float*)y, c, max_rois, pool, sampling_ratio, y_stride, level_out, sets_per_image);
+  else
+    hipLaunchKernelGGL(roi_pool_levels_sweep_kernel<__bf16>, dim3(n_sets * max_rois), dim3(256), 0, OSD_STREAM(stream), lv, boxes,
+                       counts, (__bf16*)y, c, max_rois, pool, sampling_ratio, y_stride, level_out, sets_per_image);
+  return osd_check_launch("roi_pool_levels_sweep");
 }
 
 extern "C" int osd_groupnorm_act_rois(const void* x, const void* addend, const float* gamma, const float* beta, void* y,

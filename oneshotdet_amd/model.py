@@ -240,9 +240,24 @@ def run_query_pool(qfeats, q_sizes, batch, supp_roialign=True):
     return pooled
 
 
-def run_correlate(feats, pooled):
-    """generalized_rcnn.py:307-311: all five levels in one launch."""
-    return ops.correlate_levels(feats, pooled)
+def run_correlate(feats, pooled, classes=1):
+    """generalized_rcnn.py:307-311: all five levels in one launch.  classes = K (the class sweep): pooled has K rows per image of
+    feats and the result K maps per image, row b*K + k (ops.correlate_levels_sweep: each map loaded once per group of vectors)."""
+    if classes == 1:
+        return ops.correlate_levels(feats, pooled)
+    return ops.correlate_levels_sweep(feats, pooled, classes)
+
+
+def check_classes(batch, query_rows, classes):
+    """The class sweep's row rule, checked before anything is launched: queries holds batch * classes * S rows, row
+    (b*classes + k)*S + s = shot s of category slot k of image b.  -> S."""
+    classes = int(classes)
+    if classes < 1:
+        raise ValueError("classes must be at least 1, got %d" % classes)
+    if batch * classes == 0 or query_rows == 0 or query_rows % (batch * classes) != 0:
+        raise ValueError("%d query rows are no multiple of images x classes = %d x %d = %d (queries holds B*K*S rows: S shots of each "
+                         "of K category slots per image)" % (query_rows, batch, classes, batch * classes))
+    return query_rows // (batch * classes)
 
 
 def run_head_tower(hw, feats, tower):
@@ -412,11 +427,12 @@ class HotPathEngine(object):
             self.box_head = BoxHeadWeights(self.sd, self.dtype, box_cls_loss=self.box_cls_loss, soft_labeling=self.soft_labeling,
                                            linear_fusion=self.linear_fusion, neg_support=self.neg_support)
 
-    def tune(self, images, queries, second_stage=False):
+    def tune(self, images, queries, second_stage=False, classes=1):
         """Pick, by measurement on this device, the conv algorithm (kernel generation, ring depth, tile) for every
-        distinct conv shape of this input geometry (cached in ops.ALGO_CACHE; a few ms per shape, done once)."""
+        distinct conv shape of this input geometry (cached in ops.ALGO_CACHE; a few ms per shape, done once).  classes: as detect's
+        (a sweep's head and box head run at B*K rows: other shapes than the per-pair call's)."""
         with ops.tuning():
-            self.detect(images, queries, concurrent=False, second_stage=second_stage)
+            self.detect(images, queries, concurrent=False, second_stage=second_stage, classes=classes)
         torch.cuda.synchronize()
 
     def side_streams(self):
@@ -424,11 +440,15 @@ class HotPathEngine(object):
             self._streams = [torch.cuda.Stream(device=self.device) for _ in range(3)]
         return self._streams
 
-    def forward_features(self, images, queries, concurrent=True, query_sizes=None):
+    def forward_features(self, images, queries, concurrent=True, query_sizes=None, classes=1):
         """Target backbone on the current stream; the (independent, tiny) query backbone + pooling on a side stream
         (concurrent=False: one after the other on the current stream; OSD_LOCKSTEP=1: both backbones per launch, A/B).
-        query_sizes: true (h, w) of every query of a padded batch (default: the tensor's size)."""
-        batch = images.shape[0]
+        query_sizes: true (h, w) of every query of a padded batch (default: the tensor's size).
+        classes = K (the class sweep): queries holds B*K*S rows; the target backbone runs on the B images once, the query branch pools
+        B*K category slots of S shots, and `combined` has B*K rows (b*K + k) from one sweep launch over the B-row features."""
+        if classes != 1:
+            check_classes(images.shape[0], queries.shape[0], classes)
+        batch = images.shape[0] * classes
         q_sizes = [tuple(queries.shape[-2:])] * queries.shape[0] if query_sizes is None else list(query_sizes)
         if concurrent and LOCKSTEP:
             feats, qfeats = run_backbones(self.backbone, self.supp_backbone, images, queries, self.dtype)
@@ -445,19 +465,26 @@ class HotPathEngine(object):
             feats = run_backbone(self.backbone, images, self.dtype)
             qfeats = run_backbone(self.supp_backbone, queries, self.dtype)
             pooled = run_query_pool(qfeats, q_sizes, batch, self.supp_roialign)
-        combined = run_correlate(feats, pooled)
+        combined = run_correlate(feats, pooled, classes)
         return feats, qfeats, pooled, combined
 
-    def forward(self, images, queries, concurrent=True, query_sizes=None):
-        """images [B,3,H,W], queries [B*S,3,h,w] NCHW fp32 on the device -> dict of NHWC intermediates."""
-        feats, qfeats, pooled, combined = self.forward_features(images, queries, concurrent, query_sizes)
+    def forward(self, images, queries, concurrent=True, query_sizes=None, classes=1):
+        """images [B,3,H,W], queries [B*S,3,h,w] NCHW fp32 on the device -> dict of NHWC intermediates.  classes = K: queries
+        [B*K*S,3,h,w] (forward_features); `features` keeps B rows, everything per (image, category) has B*K, and out["classes"] = K."""
+        feats, qfeats, pooled, combined = self.forward_features(images, queries, concurrent, query_sizes, classes)
         head = run_head(self.head, combined, self.side_streams() if concurrent else None)
-        return dict(features=feats, query_features=qfeats, pooled=pooled, combined=combined, head=head)
+        out = dict(features=feats, query_features=qfeats, pooled=pooled, combined=combined, head=head)
+        if classes != 1:
+            out["classes"] = classes
+        return out
 
-    def detect(self, images, queries, training=False, cuda_nms=True, concurrent=True, second_stage=False):
+    def detect(self, images, queries, training=False, cuda_nms=True, concurrent=True, second_stage=False, classes=1):
         """GeneralizedRCNN.forward in eval mode (generalized_rcnn.py:226-332): first stage -> out["proposals"] =
         (boxes [N,P,4], scores [N,P], counts [N]); with second_stage also the few-shot ROI box head ->
-        out["detections"] = dict(boxes [N,K,4], scores [N,K] descending, counts [N])."""
+        out["detections"] = dict(boxes [N,K,4], scores [N,K] descending, counts [N]).
+        classes = K (the class sweep, K category slots per image in one pass): queries holds B*K*S rows, row (b*K + k)*S + s = shot
+        s of slot k of image b; the target backbone + FPN run once per image, and every output but out["features"] has N = B*K
+        rows in the order b*K + k.  A row count that is no multiple of B*K is a ValueError before anything is launched."""
         from .layers import ImageList
         image_sizes = query_sizes = None
         if isinstance(images, ImageList):       # padded batch (R0): clip to every image's own size
@@ -468,10 +495,15 @@ class HotPathEngine(object):
             query_sizes = queries.image_sizes
         if isinstance(queries, ImageList):
             queries, query_sizes = queries.tensors, queries.image_sizes
+        if classes != 1:                        # the class sweep: the rest of this call runs on B*K rows, each image's true size K times
+            check_classes(images.shape[0], queries.shape[0], classes)
+            if image_sizes is not None:
+                image_sizes = [tuple(s) for s in image_sizes for _ in range(classes)]
+        shots = queries.shape[0] // (images.shape[0] * classes)
         if second_stage:                        # refused before anything is launched
             from .box_head import check_shots
-            check_shots(self.box_cls_loss, queries.shape[0] // images.shape[0])
-        out = self.forward(images, queries, concurrent, query_sizes)
+            check_shots(self.box_cls_loss, shots)
+        out = self.forward(images, queries, concurrent, query_sizes, classes)
         h, w = images.shape[-2:]
         pre = spec.PRE_NMS_TOP_N_TRAIN if training else spec.PRE_NMS_TOP_N_TEST
         post = spec.POST_NMS_TOP_N_TRAIN if training else spec.POST_NMS_TOP_N_TEST
@@ -479,21 +511,23 @@ class HotPathEngine(object):
         if second_stage:
             q_sizes = query_sizes if query_sizes is not None else tuple(queries.shape[-2:])
             out["detections"] = self.box_detect(out["features"], out["query_features"], q_sizes,
-                                                out["proposals"][0], out["proposals"][2], h, w,
-                                                shots=queries.shape[0] // images.shape[0], cuda_nms=cuda_nms,
-                                                image_sizes=image_sizes)
+                                                out["proposals"][0], out["proposals"][2], h, w, shots=shots, cuda_nms=cuda_nms,
+                                                image_sizes=image_sizes, classes=classes)
         return out
 
     def box_detect(self, feats, qfeats, q_size, boxes, counts, img_h, img_w, shots=1, cuda_nms=True, want_raw=False,
-                   image_sizes=None):
+                   image_sizes=None, classes=1):
         """roi_heads.box on given proposals (boxes [N,R,4] fp32, counts [N] int32 or None).  q_size: (h, w) of all queries
-        or a list with every query's true size; image_sizes: true (h, w) per image of a padded batch."""
+        or a list with every query's true size; image_sizes: true (h, w) per image of a padded batch.
+        classes = K (the class sweep): boxes / counts / image_sizes have N = B*K rows (b*K + k), feats B images, qfeats N*shots."""
         if self.box_head is None:
             raise KeyError("state_dict has no roi_heads.box.* entries: the second stage was not packed")
         from .box_head import run_box_head
         hw_dev = None if image_sizes is None else image_sizes_dev(image_sizes, boxes.device)
+        if classes != 1 and feats[0].shape[0] * classes != boxes.shape[0]:
+            raise ValueError("%d rows of proposals are not images x classes = %d x %d" % (boxes.shape[0], feats[0].shape[0], classes))
         return run_box_head(self.box_head, feats, qfeats, q_size, boxes, counts, img_h, img_w, shots=shots,
-                            cuda_nms=cuda_nms, want_raw=want_raw, img_hw=hw_dev)
+                            cuda_nms=cuda_nms, want_raw=want_raw, img_hw=hw_dev, classes=classes)
 
 
 class GraphedDetect(object):
@@ -505,7 +539,8 @@ class GraphedDetect(object):
         self.engine = engine
         self.images = images.clone()
         self.queries = queries.clone()
-        engine.tune(self.images, self.queries, second_stage=bool(kw.get("second_stage")))
+        # classes: a sweep's head and box head run at B*K rows, and those are the shapes to tune
+        engine.tune(self.images, self.queries, second_stage=bool(kw.get("second_stage")), classes=kw.get("classes", 1))
         side = torch.cuda.Stream(device=engine.device)
         side.wait_stream(_streams.current())
         with _streams.on(side):

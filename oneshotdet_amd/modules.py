@@ -156,6 +156,36 @@ def _boxlists(boxes, scores, counts, image_sizes, labels=None):
     return out
 
 
+def merge_class_detections(boxes, scores, counts, class_ids, image_sizes):
+    """The class sweep's per-(image, category slot) detections -> ONE BoxList per image, the form evaluation.eval_detection_voc takes.
+    boxes [B*K,R,4], scores [B*K,R] (descending within a row), counts [B*K], row b*K + k = slot k of image b (tensors of any device);
+    class_ids: K ids per image (B sequences, or one sequence shared by all images); image_sizes: B x (h, w).  A BoxList holds the
+    detections of all K slots with `scores` and `labels` (= the slot's id), ordered by descending score; equal scores go by slot,
+    then by rank within the slot.  An image without detections gives an empty BoxList that still has both fields.  One host read of
+    the counts, like _boxlists."""
+    n_img = len(image_sizes)
+    ids = [list(c) for c in class_ids] if n_img and isinstance(class_ids[0], (list, tuple)) else [list(class_ids)] * n_img
+    k = len(ids[0]) if ids else 0
+    if len(ids) != n_img or any(len(c) != k for c in ids) or boxes.shape[0] != n_img * k:
+        raise ValueError("merge_class_detections: %d rows of detections for %d images x %d class ids (the same number of ids for "
+                         "every image)" % (boxes.shape[0], n_img, k))
+    cnt = counts.cpu().tolist()
+    out = []
+    for b in range(n_img):
+        rows = range(b * k, (b + 1) * k)
+        bx = torch.cat([boxes[r, :cnt[r]] for r in rows], 0) if k else boxes.new_zeros((0, 4))
+        sc = torch.cat([scores[r, :cnt[r]] for r in rows], 0) if k else scores.new_zeros((0,))
+        lb = torch.cat([torch.full((cnt[r],), int(ids[b][r - b * k]), dtype=torch.int64, device=boxes.device) for r in rows], 0) \
+            if k else torch.zeros((0,), dtype=torch.int64, device=boxes.device)
+        order = torch.sort(sc, descending=True, stable=True)[1]         # stable: (slot, rank) order among equal scores
+        h, w = image_sizes[b]
+        bl = BoxList(bx[order].reshape(-1, 4), (int(w), int(h)), mode="xyxy")
+        bl.add_field("scores", sc[order])
+        bl.add_field("labels", lb[order])
+        out.append(bl)
+    return out
+
+
 class FCOSModule(nn.Module):
     """build_rpn(cfg, in_channels) for FCOS_ON (rpn/rpn.py:201-206; fcos.py:102-207), eval path."""
 
@@ -178,7 +208,9 @@ class FCOSModule(nn.Module):
 class OneShotDetector(nn.Module):
     """GeneralizedRCNN (detector/generalized_rcnn.py:55-332) in eval mode: `backbone`, `supp_backbone`, `rpn` (and the
     `roi_heads.box.*` entries when present) under the reference's names, forward -> list[BoxList] with `scores` and
-    `labels` (= target_ids[i]) like the reference returns.  The options (spec.MODEL_OPTIONS) are model.HotPathEngine's and go to
+    `labels` (= target_ids[i]) like the reference returns.  target_ids[i] may be a sequence of K ids (the same K for every image):
+    the class sweep, images_supp then holds B*K*S images (row (b*K + k)*S + s) and the result is ONE BoxList per image with the
+    detections of all K categories (merge_class_detections).  The options (spec.MODEL_OPTIONS) are model.HotPathEngine's and go to
     it as they are: which model the state_dict is of (siamese_backbone=False: no `supp_backbone`, the query goes through
     `backbone`) and how it was trained."""
 
@@ -198,6 +230,18 @@ class OneShotDetector(nn.Module):
         dev = self.engine.device
         imgs = layers.ImageList(images.tensors.to(dev, torch.float32), images.image_sizes)
         qs = layers.ImageList(images_supp.tensors.to(dev, torch.float32), images_supp.image_sizes)
+        if target_ids is not None and len(target_ids) and isinstance(target_ids[0], (list, tuple)):
+            classes = len(target_ids[0])
+            if len(target_ids) != imgs.tensors.shape[0] or any(len(t) != classes for t in target_ids):
+                raise ValueError("nested target_ids: one sequence of the same %d ids per image, for %d images"
+                                 % (classes, imgs.tensors.shape[0]))
+            with torch.no_grad():
+                out = self.engine.detect(imgs, qs, second_stage=self.second_stage, classes=classes)
+            if self.second_stage:
+                d = out["detections"]
+                return merge_class_detections(d["boxes"], d["scores"], d["counts"], target_ids, imgs.image_sizes)
+            b, s, c = out["proposals"]
+            return merge_class_detections(b, s, c, target_ids, imgs.image_sizes)
         with torch.no_grad():
             out = self.engine.detect(imgs, qs, second_stage=self.second_stage)
         if self.second_stage:

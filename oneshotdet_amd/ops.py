@@ -597,6 +597,32 @@ def correlate_levels(xs, qs):
     return ys
 
 
+def correlate_levels_sweep(xs, qs, classes):
+    """The class sweep's correlation (include/oneshotdet_hip_class_sweep.h): xs = NHWC level maps [n, H_l, W_l, C], qs = [n*classes, C]
+    fp32 per level -> [n*classes, H_l, W_l, C] per level, row b*classes + k = xs[b] * qs[b*classes + k], in ONE launch that loads
+    every map once per group of CLASS_SWEEP_GROUP query vectors.  The bits of correlate_levels on `classes` times replicated xs."""
+    _chk_dev(*xs)
+    k = len(xs)
+    n, c = xs[0].shape[0], xs[0].shape[-1]
+    classes = int(classes)
+    if classes < 1:
+        raise ValueError("classes must be at least 1, got %d" % classes)
+    assert all(x.shape[0] == n and x.shape[-1] == c and x.is_contiguous() for x in xs)
+    assert all(q.shape == (n * classes, c) and q.dtype == torch.float32 and q.is_contiguous() for q in qs)
+    ys = [torch.empty((n * classes,) + tuple(x.shape[1:]), device=x.device, dtype=x.dtype) for x in xs]
+    hws = (C.c_int32 * k)(*[x.shape[1] * x.shape[2] for x in xs])
+    _lib.call("osd_correlate_levels_sweep", k, _ptr_array(xs), _ptr_array(qs), _ptr_array(ys), hws, n, classes, c, _dt(xs[0]),
+              _stream())
+    for x, q, y in zip(xs, qs, ys):
+        _rec("correlate_sweep", x=x, q=q, out=y, classes=classes)
+    return ys
+
+
+def class_sweep_group():
+    """Query vectors per workgroup of correlate_levels_sweep (OSD_CLASS_SWEEP_GROUP of the built library)."""
+    return int(_lib.load().osd_class_sweep_group())
+
+
 def correlate_bwd_query_levels(gs, feats):
     """dq_l[n][c] = sum_p g_l[n,p,c] * feat_l[n,p,c] for every level in one launch -> list of [n, c] fp32."""
     k = len(gs)
@@ -1268,9 +1294,10 @@ def groupnorm_relu_bwd_levels(us, dts, ab, gamma, beta, dgamma, dbeta, groups=32
 
 
 # ---- second-stage ROI box head ----
-def roi_pool_levels(feats, scales, boxes, counts, pool, sampling_ratio, out=None, want_levels=False):
+def roi_pool_levels(feats, scales, boxes, counts, pool, sampling_ratio, out=None, want_levels=False, sets_per_image=1):
     """Pooler.forward (modeling/poolers.py:93-124): feats = NHWC level maps, boxes [N,R,4] fp32 xyxy, counts [N] int32 or
-    None -> [N*R, pool, pool, C] in the maps' dtype (zero rows past counts[image])."""
+    None -> [N*R, pool, pool, C] in the maps' dtype (zero rows past counts[image]).  sets_per_image = K (the class sweep): the maps
+    have N / K images and ROI set j reads image j // K (osd_roi_pool_levels_sweep)."""
     _chk_dev(boxes, counts, *feats)
     n, r, _ = boxes.shape
     c = feats[0].shape[-1]
@@ -1282,6 +1309,13 @@ def roi_pool_levels(feats, scales, boxes, counts, pool, sampling_ratio, out=None
     hs = (C.c_int32 * k)(*[f.shape[1] for f in feats])
     ws = (C.c_int32 * k)(*[f.shape[2] for f in feats])
     sc = (C.c_float * k)(*[float(s) for s in scales])
+    if sets_per_image != 1:
+        if sets_per_image < 1 or n % sets_per_image != 0:
+            raise ValueError("%d ROI sets are no multiple of sets_per_image = %d" % (n, sets_per_image))
+        assert all(f.shape[0] * sets_per_image == n and f.shape[-1] == c and f.is_contiguous() for f in feats)
+        _lib.call("osd_roi_pool_levels_sweep", k, xs, hs, ws, sc, _ptr(boxes.contiguous()), _p(counts), _p(out), n, sets_per_image,
+                  c, r, pool, sampling_ratio, out.shape[-1], _p(lv), _dt(out), _stream())
+        return (out, lv) if want_levels else out
     assert all(f.shape[0] == n and f.shape[-1] == c and f.is_contiguous() for f in feats)
     _lib.call("osd_roi_pool_levels", k, xs, hs, ws, sc, _ptr(boxes.contiguous()), _p(counts), _p(out), n, c, r, pool,
               sampling_ratio, out.shape[-1], _p(lv), _dt(out), _stream())
