@@ -4,6 +4,7 @@
                               [--shared-backbone] [--no-supp-roialign] [--box-cls-loss ce_loss|focal_loss|mse_loss|l1_loss|cxe_loss]
                               [--soft-labeling]       # the model was trained with FEW_SHOT.SOFT_LABELING (needed for l1_loss / cxe_loss)
                               [--classes K]           # the class sweep: K categories per image in one pass, one merged BoxList per image
+                              [--gallery G]           # the query gallery: enroll G supports once, then detect image batches against the bank
     python examples/detect.py --checkpoint model_0930.pth --shared-backbone --no-supp-roialign      # the 0930 model
 
   * weights: a reference `.pth` (utils/checkpoint.py format), a Detectron ResNet `.pkl` for the backbones, or — there is no
@@ -16,7 +17,10 @@
     a common /32 size and keeps the true sizes (data/collate_batch.py + structures/image_list.py of the reference);
   * output: one BoxList per target image (boxes, scores, labels = the query's class id), like `GeneralizedRCNN.forward`;
   * --classes K: every image is asked about K categories at once (K supports per image, `target_ids` = K ids per image): the target
-    backbone runs once per image, and the BoxList of an image holds the detections of all K categories in descending score order.
+    backbone runs once per image, and the BoxList of an image holds the detections of all K categories in descending score order;
+  * --gallery G: the deployment form of the sweep.  `det.enroll(supports, labels)` runs the query branch ONCE for G categories and
+    returns a QueryBank; every later `det(images, bank, target_ids=...)` runs no query backbone at all.  target_ids names, per image,
+    the labels to look for (None: all G).
 """
 import argparse
 import os
@@ -50,6 +54,9 @@ def main():
     ap.add_argument("--classes", type=int, default=1,
                     help="K: ask every image about K categories in one pass (the class sweep, detect(..., classes=K)); the supports "
                          "are synthetic here")
+    ap.add_argument("--gallery", type=int, default=0,
+                    help="G: enroll G synthetic supports once (OneShotDetector.enroll) and detect three batches of images against the "
+                         "bank, each asking for its own labels")
     args = ap.parse_args()
     siamese = not args.shared_backbone
     roialign = not args.no_supp_roialign
@@ -86,6 +93,26 @@ def main():
     images = layers.to_image_list(targets, size_divisible=spec.SIZE_DIVISIBILITY)
     images_supp = layers.to_image_list(queries, size_divisible=spec.SIZE_DIVISIBILITY)
     print("padded batch", tuple(images.tensors.shape), "true sizes", images.image_sizes)
+    if args.gallery > 0:
+        G = args.gallery
+        sizes = [(127, 127), (96, 160)]
+        supports = [torch.from_numpy(synth.make_images("ex.g%d" % g, 1, *sizes[g % 2])[0]) for g in range(G)]
+        labels = [1 + (7 * g) % 80 for g in range(G)]
+        bank = det.enroll(layers.to_image_list(supports, size_divisible=spec.SIZE_DIVISIBILITY), labels)       # the query branch, once
+        print("enrolled %d gallery slots, labels %s" % (bank.slots, labels))
+        K = min(3, G)
+        for step in range(3):                                    # a stream of image batches against the same bank
+            batch = [torch.from_numpy(synth.make_images("ex.t%d.%d" % (step, i), 1, h, w)[0]) for i, (h, w) in enumerate([(480, 640), (512, 384)])]
+            # step 0 asks for every label; later steps for K labels per image of their own
+            ids = None if step == 0 else [[labels[(step + b + k) % G] for k in range(K)] for b in range(2)]
+            results = det(layers.to_image_list(batch, size_divisible=spec.SIZE_DIVISIBILITY), bank, target_ids=ids)
+            torch.cuda.synchronize()
+            for i, bl in enumerate(results):
+                got = bl.get_field("labels").cpu().tolist()
+                print("batch %d image %d: %s for labels %s, top score %.3f (label %s)" % (
+                    step, i, bl, "all" if ids is None else ids[i], float(bl.get_field("scores")[0]) if len(bl) else float("nan"),
+                    got[0] if got else "-"))
+        return
     if args.classes > 1:
         # K supports per image, row b*K + k = category slot k of image b (synthetic: no two alike), and K class ids per image
         K = args.classes

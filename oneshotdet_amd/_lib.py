@@ -164,6 +164,12 @@ SIGNATURES_CLASS_SWEEP = {
     "osd_roi_pool_levels_sweep": (_i, [_i, _p, _p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _i, _p]),
 }
 
+# include/oneshotdet_hip_gallery.h: the query gallery (supports enrolled once, read through a slot table), a seventh table
+SIGNATURES_GALLERY = {
+    "osd_correlate_levels_gallery": (_i, [_i, _p, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "osd_groupnorm_act_rois_gallery": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _i, _i, _i, _i, _i, _p]),
+}
+
 _lib = None
 
 
@@ -184,7 +190,7 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_BOX_MODES.items()) + list(SIGNATURES_SOFT_LABELS.items())
                               + list(SIGNATURES_NEG_SUPPORT.items()) + list(SIGNATURES_SOLVER.items())
-                              + list(SIGNATURES_CLASS_SWEEP.items())):
+                              + list(SIGNATURES_CLASS_SWEEP.items()) + list(SIGNATURES_GALLERY.items())):
         fn = getattr(lib, name)   # AttributeError if the symbol is missing
         fn.restype = res
         fn.argtypes = args

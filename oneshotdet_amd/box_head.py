@@ -94,21 +94,39 @@ def run_query_roi(qfeats, q_size, dtype):
     return ops.roi_pool_levels(qfeats, spec.POOLER_SCALES, boxes, None, spec.BOX_POOL, spec.POOLER_SAMPLING_RATIO)
 
 
+def run_query_half(bw, qfeats, q_size, dtype):
+    """The query's share of the head in front of fc6: supproi_pooling, then the query half of the split first conv.
+    -> (q [N*S,7,7,C], q_half [N*S,7,7,512 | 128] = W_q q + b).  What HotPathEngine.enroll keeps in a QueryBank."""
+    q = run_query_roi(qfeats, q_size, dtype)
+    # FEW_SHOT.LINEAR_FUSION (box_head.py:61-72,148): the head in front of fc6 is the split 3x3 conv, GroupNorm, LeakyReLU
+    conv_q, pad = (bw.aggreg_q, 1) if bw.linear_fusion else (bw.conv0_q, 0)
+    return q, ops.conv2d(q, conv_q, pad=pad)
+
+
 def run_box_head(bw, feats, qfeats, q_size, boxes, counts, img_h, img_w, shots=1, cuda_nms=True, want_raw=False, img_hw=None,
-                 classes=1):
+                 classes=1, bank=None, slots=None):
     """feats / qfeats: NHWC P3..P7 of the target / query backbone; boxes [N,R,4], counts [N] = first-stage proposals.
     Returns dict(boxes [N,K,4], scores [N,K] descending, counts [N]) (+ raw logits / deltas / pooled maps).
     classes = K (the class sweep): N = B*K rows of proposals (row b*K + k), feats has B images, qfeats B*K*shots, img_hw N rows; the
-    ROI pooling reads image row // K and everything after it is the per-pair head on N rows."""
+    ROI pooling reads image row // K and everything after it is the per-pair head on N rows.
+    bank + slots (the query gallery; qfeats and q_size unused): the query halves are rows of bank.q_half, [G*shots] maps enrolled once,
+    picked by the device int32 [N] table: row slots[j]*shots + s for ROI set j.  They are gathered by one index_select and go to the
+    existing GroupNorm entry: osd_groupnorm_act_rois_gallery, which reads them through the table, measured 1 % SLOWER than that
+    composition at bs 4 and 8 (profiles/query_bank.md), so it is not on this path (ops.groupnorm_act_rois(add_index=) is the entry).
+    No query backbone, pooling or conv launch either way."""
     n, r, _ = boxes.shape
     dtype = feats[0].dtype
     check_shots(bw.box_cls_loss, shots)                                                # nothing has been launched yet
-    q = run_query_roi(qfeats, q_size, dtype)                                           # [N*S,7,7,C]
-    assert q.shape[0] == n * shots
     linear = bw.linear_fusion
-    # FEW_SHOT.LINEAR_FUSION (box_head.py:61-72,148): the head in front of fc6 is the split 3x3 conv, GroupNorm, LeakyReLU
-    conv_q, conv_x, pad = (bw.aggreg_q, bw.aggreg_x, 1) if linear else (bw.conv0_q, bw.conv0_x, 0)
-    q_half = ops.conv2d(q, conv_q, pad=pad)                                            # [N*S,7,7,512 | 128]  W_q q + b
+    conv_x, pad = (bw.aggreg_x, 1) if linear else (bw.conv0_x, 0)
+    if bank is not None:
+        assert bank.shots == shots and slots.shape == (n,)
+        rows = slots if shots == 1 else (slots[:, None] * shots + torch.arange(shots, device=slots.device, dtype=slots.dtype)).reshape(-1)
+        q_half = bank.q_half.index_select(0, rows)                                     # [N*S,7,7,512 | 128], on the device
+        q = bank.query_roi.index_select(0, rows) if want_raw else None
+    else:
+        q, q_half = run_query_half(bw, qfeats, q_size, dtype)                          # [N*S,7,7,C], [N*S,7,7,512 | 128]  W_q q + b
+        assert q.shape[0] == n * shots
     x = ops.roi_pool_levels(feats, spec.POOLER_SCALES, boxes, counts, spec.BOX_POOL, spec.POOLER_SAMPLING_RATIO,
                             sets_per_image=classes)
     u0 = ops.conv2d(x, conv_x, pad=pad)                                                # [N*R,7,7,512 | 128]  W_x x, once for all shots

@@ -5,6 +5,7 @@
 //                                                                    modeling/box_coder.py:50-95)
 // All HBM-bound.  The convolutions / fully connected layers of the head run on the implicit-GEMM kernels.
 #include "osd_common.h"
+#include "gn_act_rois.h"
 #include "../../include/oneshotdet_hip_box_modes.h"
 #include "../../include/oneshotdet_hip_class_sweep.h"
 
@@ -43,26 +44,6 @@ template <> struct Chunk<__bf16> {
     *reinterpret_cast<bf16x8*>(p) = t;
   }
 };
-
-// two adjacent channels (even index) as one 4- / 8-byte access
-__device__ __forceinline__ void load2(const float* p, float& a, float& b) {
-  const f32x2 t = *reinterpret_cast<const f32x2*>(p);
-  a = t[0]; b = t[1];
-}
-__device__ __forceinline__ void load2(const __bf16* p, float& a, float& b) {
-  const uint32_t u = *reinterpret_cast<const uint32_t*>(p);
-  a = __uint_as_float(u << 16);
-  b = __uint_as_float(u & 0xffff0000u);
-}
-__device__ __forceinline__ void store2(float* p, float a, float b) {
-  f32x2 t = {a, b};
-  *reinterpret_cast<f32x2*>(p) = t;
-}
-__device__ __forceinline__ void store2(__bf16* p, float a, float b) {
-  typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-  bf16x2 t = {(__bf16)a, (__bf16)b};
-  *reinterpret_cast<bf16x2*>(p) = t;
-}
 
 struct PoolLevels {
   const void* x[OSD_MAX_ROI_LEVELS];
@@ -215,59 +196,7 @@ __global__ __launch_bounds__(256) void roi_pool_levels_sweep_kernel(PoolLevels l
   roi_pool_levels_body<T>(lv, boxes, counts, y, c, max_rois, pool, sampling, y_stride, level_out, sets_per_image);
 }
 
-// GroupNorm(groups, C) + LeakyReLU(slope) of one ROI map [hw][C] per workgroup (hw = 49): the whole sample sits in
-// registers, so mean and the centred second moment are two exact passes over registers and HBM is read once.
-// Thread t owns channels (2t, 2t+1) of every pixel; a group's channels are CPG/2 adjacent lanes.  `addend` (optional):
-// [n_add][hw][C], row of this sample = sample / rois_per_add * add_stride + add_offset — the query half of the
-// concatenated 1x1 conv (box_head.py:146-148), which is the same for every ROI of an image, added before the statistics.
-template <typename T, int HW>
-__global__ __launch_bounds__(256) void gn_act_rois_kernel(const T* __restrict__ x, const T* __restrict__ addend,
-                                                          const float* __restrict__ gamma, const float* __restrict__ beta,
-                                                          T* __restrict__ y, int c, int groups, float eps, float slope,
-                                                          int rois_per_add, int add_stride, int add_offset) {
-  const int sample = blockIdx.x;
-  const int t = threadIdx.x;                 // blockDim.x == c / 2
-  const int cpg = c / groups;                // channels per group (even)
-  const int lanes = cpg / 2;                 // lanes per group: power of two <= 64
-  const T* xs = x + (size_t)sample * HW * c + 2 * t;
-  float v0[HW], v1[HW];
-#pragma unroll
-  for (int p = 0; p < HW; ++p) load2(xs + (size_t)p * c, v0[p], v1[p]);
-  if (addend) {
-    const T* as = addend + ((size_t)(sample / rois_per_add) * add_stride + add_offset) * HW * c + 2 * t;
-#pragma unroll
-    for (int p = 0; p < HW; ++p) {
-      float a0, a1;
-      load2(as + (size_t)p * c, a0, a1);
-      v0[p] += a0;
-      v1[p] += a1;
-    }
-  }
-  float s = 0.f;
-#pragma unroll
-  for (int p = 0; p < HW; ++p) s += v0[p] + v1[p];
-  for (int m = 1; m < lanes; m <<= 1) s += __shfl_xor(s, m);
-  const float inv_n = 1.f / (float)(HW * cpg);
-  const float mean = s * inv_n;
-  float q = 0.f;
-#pragma unroll
-  for (int p = 0; p < HW; ++p) {
-    const float d0 = v0[p] - mean, d1 = v1[p] - mean;
-    q += d0 * d0 + d1 * d1;
-  }
-  for (int m = 1; m < lanes; m <<= 1) q += __shfl_xor(q, m);
-  const float rstd = rsqrtf(q * inv_n + eps);
-  const float a0 = gamma[2 * t] * rstd, a1 = gamma[2 * t + 1] * rstd;
-  const float b0 = beta[2 * t] - mean * a0, b1 = beta[2 * t + 1] - mean * a1;
-  T* ys = y + (size_t)sample * HW * c + 2 * t;
-#pragma unroll
-  for (int p = 0; p < HW; ++p) {
-    float o0 = fmaf(v0[p], a0, b0), o1 = fmaf(v1[p], a1, b1);
-    o0 = o0 >= 0.f ? o0 : o0 * slope;
-    o1 = o1 >= 0.f ? o1 : o1 * slope;
-    store2(ys + (size_t)p * c, o0, o1);
-  }
-}
+// (GroupNorm(groups, C) + LeakyReLU(slope) of one ROI map per workgroup: gn_act_rois.h, shared with the query gallery's entry.)
 
 // Per ROI: arg-max over the shots of each class logit and the box deltas that go with it (box_head.py:239-252),
 // softmax over the two logits (inference.py:66), BoxCoder.decode of the class-1 deltas (box_coder.py:50-95), clip to
@@ -477,22 +406,17 @@ extern "C" int osd_groupnorm_act_rois(const void* x, const void* addend, const f
                                       int n_samples, int hw, int c, int groups, float eps, float slope, int rois_per_add,
                                       int add_stride, int add_offset, int dtype, void* stream) {
   if (!x || !gamma || !beta || !y) return osd_fail(OSD_ERR_INVALID_ARG, "groupnorm_act_rois: null argument");
-  if (hw != 49) return osd_fail(OSD_ERR_UNSUPPORTED, "groupnorm_act_rois: hw %d (only 7x7 ROI maps)", hw);
-  const int cpg = groups > 0 ? c / groups : 0;
-  const int lanes = cpg / 2;
-  if (groups < 1 || c % groups != 0 || cpg % 2 != 0 || lanes < 1 || lanes > 64 || (lanes & (lanes - 1)) != 0 || c > 512 ||
-      (c / 2) % 64 != 0)
-    return osd_fail(OSD_ERR_UNSUPPORTED, "groupnorm_act_rois: c %d groups %d", c, groups);
+  if (const int rc = gn_act_rois_shape("groupnorm_act_rois", hw, c, groups)) return rc;
   if (addend && rois_per_add < 1) return osd_fail(OSD_ERR_INVALID_ARG, "groupnorm_act_rois: rois_per_add");
   if (n_samples == 0) return OSD_OK;
   if (dtype == OSD_F32)
-    hipLaunchKernelGGL((gn_act_rois_kernel<float, 49>), dim3(n_samples), dim3(c / 2), 0, OSD_STREAM(stream), (const float*)x,
+    hipLaunchKernelGGL((gn_act_rois_kernel<float, 49, false>), dim3(n_samples), dim3(c / 2), 0, OSD_STREAM(stream), (const float*)x,
                        (const float*)addend, gamma, beta, (float*)y, c, groups, eps, slope, rois_per_add, add_stride,
-                       add_offset);
+                       add_offset, (const int32_t*)nullptr, 0, 0);
   else if (dtype == OSD_BF16)
-    hipLaunchKernelGGL((gn_act_rois_kernel<__bf16, 49>), dim3(n_samples), dim3(c / 2), 0, OSD_STREAM(stream),
+    hipLaunchKernelGGL((gn_act_rois_kernel<__bf16, 49, false>), dim3(n_samples), dim3(c / 2), 0, OSD_STREAM(stream),
                        (const __bf16*)x, (const __bf16*)addend, gamma, beta, (__bf16*)y, c, groups, eps, slope, rois_per_add,
-                       add_stride, add_offset);
+                       add_stride, add_offset, (const int32_t*)nullptr, 0, 0);
   else
     return osd_fail(OSD_ERR_INVALID_ARG, "bad dtype %d", dtype);
   return osd_check_launch("groupnorm_act_rois");

@@ -240,12 +240,109 @@ def run_query_pool(qfeats, q_sizes, batch, supp_roialign=True):
     return pooled
 
 
-def run_correlate(feats, pooled, classes=1):
+def run_correlate(feats, pooled, classes=1, bank=None, slots=None):
     """generalized_rcnn.py:307-311: all five levels in one launch.  classes = K (the class sweep): pooled has K rows per image of
-    feats and the result K maps per image, row b*K + k (ops.correlate_levels_sweep: each map loaded once per group of vectors)."""
+    feats and the result K maps per image, row b*K + k (ops.correlate_levels_sweep: each map loaded once per group of vectors).
+    bank + slots (the query gallery): the K vectors of an image are rows of bank.pooled picked by the device slot table
+    (ops.correlate_levels_gallery); `pooled` is not read and no query launch is made."""
+    if bank is not None:
+        return ops.correlate_levels_gallery(feats, bank.pooled, slots, classes)
     if classes == 1:
         return ops.correlate_levels(feats, pooled)
     return ops.correlate_levels_sweep(feats, pooled, classes)
+
+
+class QueryBank(object):
+    """What HotPathEngine.enroll keeps of G gallery slots of S shots each, so that no later call runs the query branch:
+      pooled     5 x [G, C] fp32           the pooled query vectors the correlation multiplies by (run_query_pool)
+      q_half     [G*S, 7, 7, 512 | 128]    W_q q + b of the box head's first conv (None without a packed second stage)
+      query_roi  [G*S, 7, 7, C]            the pooled query maps behind q_half (box_detect's want_raw)
+      shots, slots = G, labels (one per slot, or None), dtype, and the engine + the token of its packed weights the data was computed
+    with.  Lives in device memory of this process only: it is refused after engine.repack() and by any other engine."""
+
+    def __init__(self, engine, token, pooled, q_half, query_roi, shots, slots, labels, dtype):
+        self.engine, self.token = engine, token
+        self.pooled, self.q_half, self.query_roi = pooled, q_half, query_roi
+        self.shots, self.slots, self.labels, self.dtype = shots, slots, labels, dtype
+
+    def slots_of(self, target_ids, batch):
+        """Labels -> slot numbers (a label's slot is its position in `labels`).  target_ids: None (every slot in order), or one
+        sequence of labels per image.  -> class_ids for detect (None, or `batch` lists of slot numbers)."""
+        if target_ids is None:
+            return None
+        if self.labels is None:
+            raise ValueError("this QueryBank was enrolled without labels: target_ids cannot name its slots")
+        if len(target_ids) != batch or not all(isinstance(t, (list, tuple)) for t in target_ids):
+            raise ValueError("target_ids with a QueryBank: one sequence of labels per image, for %d images (got %d entries)"
+                             % (batch, len(target_ids)))
+        where = {label: i for i, label in enumerate(self.labels)}
+        for b, row in enumerate(target_ids):
+            for label in row:
+                if label not in where:
+                    raise ValueError("target_ids[%d] names label %r, which is not among the bank's labels %s" % (b, label, list(self.labels)))
+        return [[where[label] for label in row] for row in target_ids]
+
+
+def check_class_ids(engine, bank, batch, class_ids, second_stage=False):
+    """Everything detect(bank=, class_ids=) can refuse, on the host and before anything is launched: the bank (a QueryBank of this
+    engine's dtype, of this engine, of its current packed weights; one shot per slot in the one-logit loss modes when the second stage
+    runs) and the table (None = every slot in order, or one sequence of K slot numbers in [0, G) per image, the same K for every image;
+    repeats allowed).  -> (K, the table as a flat tuple, row b*K + k)."""
+    if not isinstance(bank, QueryBank):
+        raise ValueError("bank must be a QueryBank made by HotPathEngine.enroll, got %s" % type(bank).__name__)
+    if bank.dtype != engine.dtype:
+        raise ValueError("the QueryBank holds %s data and this engine computes in %s: enroll the supports with this engine"
+                         % (bank.dtype, engine.dtype))
+    if bank.engine is not engine:
+        raise ValueError("the QueryBank was enrolled by another engine: its vectors come from other weights (enroll the supports with "
+                         "this engine)")
+    if bank.token != engine.pack_token:
+        raise ValueError("stale QueryBank: it was enrolled before repack() (weights token %d, the engine's is %d); enroll the supports "
+                         "again" % (bank.token, engine.pack_token))
+    if second_stage:
+        from .box_head import check_shots
+        check_shots(engine.box_cls_loss, bank.shots)
+    g = bank.slots
+    if class_ids is None:
+        return g, tuple(range(g)) * batch
+    rows = []
+    for r in class_ids:
+        r = r.tolist() if hasattr(r, "tolist") else r
+        if not isinstance(r, (list, tuple, range)):
+            raise ValueError("class_ids must be one sequence of slot numbers per image (nested), got a flat sequence")
+        rows.append(list(r))
+    if len(rows) != batch:
+        raise ValueError("class_ids has %d rows for %d images (one sequence of slot numbers per image)" % (len(rows), batch))
+    k = len(rows[0]) if rows else 0
+    if any(len(r) != k for r in rows):
+        raise ValueError("ragged class_ids: rows of %s slot numbers (the same K for every image)" % sorted(set(len(r) for r in rows)))
+    if k < 1:
+        raise ValueError("class_ids rows are empty: at least one slot per image")
+    for b, r in enumerate(rows):
+        for v in r:
+            if int(v) != v or not 0 <= int(v) < g:
+                raise ValueError("class_ids[%d] holds slot %r: not in [0, %d), the bank's %d slots" % (b, v, g, g))
+    return k, tuple(int(v) for r in rows for v in r)
+
+
+_SLOT_CACHE = {}
+
+
+def slot_table_dev(flat, device):
+    """The slot table on the device (int32 [B*K]), cached by content like the ROI table: no host->device copy in steady state and
+    none inside a hipGraph capture."""
+    key = (flat, str(device))
+    if key not in _SLOT_CACHE:
+        _SLOT_CACHE[key] = torch.tensor(flat, dtype=torch.int32, device=device)
+    return _SLOT_CACHE[key]
+
+
+class SlotTable(object):
+    """A validated slot table: K, the host rows and the device int32 [B*K] the kernels read.  What check_class_ids + slot_table_dev
+    give; GraphedDetect passes one whose device tensor is its own static buffer as `class_ids`."""
+
+    def __init__(self, classes, ids, dev):
+        self.classes, self.ids, self.dev = classes, ids, dev
 
 
 def check_classes(batch, query_rows, classes):
@@ -414,6 +511,7 @@ class HotPathEngine(object):
         self.repack()
 
     def repack(self):
+        self.pack_token = getattr(self, "pack_token", 0) + 1      # a QueryBank enrolled with the weights packed before is stale
         self.backbone = BackboneWeights(self.sd, "backbone.", self.dtype)
         # shared mode: the query branch runs on the target's packed weights (nothing packed, copied or tuned twice)
         self.supp_backbone = BackboneWeights(self.sd, "supp_backbone.", self.dtype) if self.siamese_backbone else self.backbone
@@ -427,25 +525,76 @@ class HotPathEngine(object):
             self.box_head = BoxHeadWeights(self.sd, self.dtype, box_cls_loss=self.box_cls_loss, soft_labeling=self.soft_labeling,
                                            linear_fusion=self.linear_fusion, neg_support=self.neg_support)
 
-    def tune(self, images, queries, second_stage=False, classes=1):
+    def tune(self, images, queries=None, second_stage=False, classes=1, bank=None, class_ids=None):
         """Pick, by measurement on this device, the conv algorithm (kernel generation, ring depth, tile) for every
         distinct conv shape of this input geometry (cached in ops.ALGO_CACHE; a few ms per shape, done once).  classes: as detect's
-        (a sweep's head and box head run at B*K rows: other shapes than the per-pair call's)."""
+        (a sweep's head and box head run at B*K rows: other shapes than the per-pair call's); bank / class_ids: as detect's."""
         with ops.tuning():
-            self.detect(images, queries, concurrent=False, second_stage=second_stage, classes=classes)
+            self.detect(images, queries, concurrent=False, second_stage=second_stage, classes=classes, bank=bank, class_ids=class_ids)
         torch.cuda.synchronize()
+
+    def enroll(self, queries, shots=1, labels=None):
+        """The query branch, once: queries [G*S,3,h,w] (or an ImageList / ops.PackedImages of G*S supports), row g*S + s = shot s of
+        gallery slot g -> QueryBank.  Runs what detect runs per call on its queries (the query backbone + FPN, the query pooling, and
+        with a packed second stage supproi_pooling and the query half of the box head's first conv), keeps the results, and
+        detect(images, bank=bank, class_ids=...) then launches none of them.  labels: one (hashable) label per slot, for
+        OneShotDetector's target_ids."""
+        from .layers import ImageList
+        query_sizes = None
+        if isinstance(queries, ops.PackedImages):
+            query_sizes = queries.image_sizes
+        if isinstance(queries, ImageList):
+            queries, query_sizes = queries.tensors, queries.image_sizes
+        shots = int(shots)
+        rows = queries.shape[0]
+        if shots < 1 or rows == 0 or rows % shots != 0:
+            raise ValueError("%d support rows are no multiple of shots = %d (queries holds G*S rows: S shots of each of G gallery slots)"
+                             % (rows, shots))
+        g = rows // shots
+        if labels is not None:
+            labels = list(labels)
+            if len(labels) != g or len(set(labels)) != g:
+                raise ValueError("labels: one distinct label per gallery slot, %d slots (got %d labels, %d distinct)"
+                                 % (g, len(labels), len(set(labels))))
+        q_sizes = [tuple(queries.shape[-2:])] * rows if query_sizes is None else list(query_sizes)
+        qfeats = run_backbone(self.supp_backbone, queries, self.dtype)
+        pooled = run_query_pool(qfeats, q_sizes, g, self.supp_roialign)
+        q_half = query_roi = None
+        if self.box_head is not None:
+            from .box_head import run_query_half
+            query_roi, q_half = run_query_half(self.box_head, qfeats, q_sizes if query_sizes is not None else q_sizes[0], self.dtype)
+        return QueryBank(self, self.pack_token, pooled, q_half, query_roi, shots, g, labels, self.dtype)
+
+    def slot_table(self, bank, batch, class_ids, second_stage=False):
+        """check_class_ids + the cached device table -> SlotTable (a SlotTable passes through: its rows were validated when it was
+        made, the bank is checked again)."""
+        if isinstance(class_ids, SlotTable):
+            check_class_ids(self, bank, batch, None, second_stage)
+            if class_ids.dev.shape != (batch * class_ids.classes,):
+                raise ValueError("the slot table holds %d entries for %d images x %d slots" % (class_ids.dev.numel(), batch, class_ids.classes))
+            return class_ids
+        k, flat = check_class_ids(self, bank, batch, class_ids, second_stage)
+        return SlotTable(k, [list(flat[b * k:(b + 1) * k]) for b in range(batch)], slot_table_dev(flat, self.device))
 
     def side_streams(self):
         if getattr(self, "_streams", None) is None:
             self._streams = [torch.cuda.Stream(device=self.device) for _ in range(3)]
         return self._streams
 
-    def forward_features(self, images, queries, concurrent=True, query_sizes=None, classes=1):
+    def forward_features(self, images, queries=None, concurrent=True, query_sizes=None, classes=1, bank=None, class_ids=None):
         """Target backbone on the current stream; the (independent, tiny) query backbone + pooling on a side stream
         (concurrent=False: one after the other on the current stream; OSD_LOCKSTEP=1: both backbones per launch, A/B).
         query_sizes: true (h, w) of every query of a padded batch (default: the tensor's size).
         classes = K (the class sweep): queries holds B*K*S rows; the target backbone runs on the B images once, the query branch pools
-        B*K category slots of S shots, and `combined` has B*K rows (b*K + k) from one sweep launch over the B-row features."""
+        B*K category slots of S shots, and `combined` has B*K rows (b*K + k) from one sweep launch over the B-row features.
+        bank (+ class_ids, see detect) instead of queries: only the target backbone runs; `combined` is one gallery launch over the
+        bank's pooled vectors, and the query features returned are None."""
+        if bank is not None or queries is None:
+            table = self._bank_table(images.shape[0], queries, bank, class_ids, classes)
+            feats = run_backbone(self.backbone, images, self.dtype)
+            return feats, None, bank.pooled, run_correlate(feats, None, table.classes, bank=bank, slots=table.dev)
+        if class_ids is not None:
+            raise ValueError("class_ids picks slots of a QueryBank: give bank= instead of queries")
         if classes != 1:
             check_classes(images.shape[0], queries.shape[0], classes)
         batch = images.shape[0] * classes
@@ -468,29 +617,67 @@ class HotPathEngine(object):
         combined = run_correlate(feats, pooled, classes)
         return feats, qfeats, pooled, combined
 
-    def forward(self, images, queries, concurrent=True, query_sizes=None, classes=1):
+    def _bank_table(self, batch, queries, bank, class_ids, classes=1, second_stage=False):
+        """The bank form's refusals (nothing launched yet) -> SlotTable."""
+        if (queries is None) == (bank is None):
+            raise ValueError("exactly one of queries and bank must be given (got %s)" % ("both" if bank is not None else "neither"))
+        table = self.slot_table(bank, batch, class_ids, second_stage)
+        if classes not in (1, table.classes):
+            raise ValueError("classes = %d, but class_ids asks for %d slots per image (with a bank, leave classes alone)"
+                             % (classes, table.classes))
+        return table
+
+    def forward(self, images, queries=None, concurrent=True, query_sizes=None, classes=1, bank=None, class_ids=None):
         """images [B,3,H,W], queries [B*S,3,h,w] NCHW fp32 on the device -> dict of NHWC intermediates.  classes = K: queries
-        [B*K*S,3,h,w] (forward_features); `features` keeps B rows, everything per (image, category) has B*K, and out["classes"] = K."""
-        feats, qfeats, pooled, combined = self.forward_features(images, queries, concurrent, query_sizes, classes)
+        [B*K*S,3,h,w] (forward_features); `features` keeps B rows, everything per (image, category) has B*K, and out["classes"] = K.
+        bank / class_ids: as detect's; out["classes"] = K, out["class_ids"] = the table's rows, and there is no out["query_features"]."""
+        if bank is not None or queries is None:
+            table = self._bank_table(images.shape[0], queries, bank, class_ids, classes)
+            feats, _, pooled, combined = self.forward_features(images, None, concurrent, None, classes, bank, table)
+            head = run_head(self.head, combined, self.side_streams() if concurrent else None)
+            return dict(features=feats, pooled=pooled, combined=combined, head=head, classes=table.classes, class_ids=table.ids)
+        feats, qfeats, pooled, combined = self.forward_features(images, queries, concurrent, query_sizes, classes, None, class_ids)
         head = run_head(self.head, combined, self.side_streams() if concurrent else None)
         out = dict(features=feats, query_features=qfeats, pooled=pooled, combined=combined, head=head)
         if classes != 1:
             out["classes"] = classes
         return out
 
-    def detect(self, images, queries, training=False, cuda_nms=True, concurrent=True, second_stage=False, classes=1):
+    def detect(self, images, queries=None, training=False, cuda_nms=True, concurrent=True, second_stage=False, classes=1, bank=None,
+               class_ids=None):
         """GeneralizedRCNN.forward in eval mode (generalized_rcnn.py:226-332): first stage -> out["proposals"] =
         (boxes [N,P,4], scores [N,P], counts [N]); with second_stage also the few-shot ROI box head ->
         out["detections"] = dict(boxes [N,K,4], scores [N,K] descending, counts [N]).
         classes = K (the class sweep, K category slots per image in one pass): queries holds B*K*S rows, row (b*K + k)*S + s = shot
         s of slot k of image b; the target backbone + FPN run once per image, and every output but out["features"] has N = B*K
-        rows in the order b*K + k.  A row count that is no multiple of B*K is a ValueError before anything is launched."""
+        rows in the order b*K + k.  A row count that is no multiple of B*K is a ValueError before anything is launched.
+        bank (the query gallery, instead of queries: exactly one of the two): a QueryBank from enroll(); class_ids = one sequence of K
+        slot numbers per image (the same K for every image, repeats allowed), None = every slot in order (K = G).  Rows are b*K + k
+        as with classes=K, out["classes"] = K, out["class_ids"] the table, no out["query_features"]; no query backbone, query pooling or
+        query-half conv is launched.  check_class_ids refuses a bad table or bank (ValueError) before anything is launched."""
         from .layers import ImageList
         image_sizes = query_sizes = None
         if isinstance(images, ImageList):       # padded batch (R0): clip to every image's own size
             images, image_sizes = images.tensors, images.image_sizes
         elif isinstance(images, ops.PackedImages):
             image_sizes = images.image_sizes
+        if bank is not None or queries is None:
+            table = self._bank_table(images.shape[0], queries, bank, class_ids, classes, second_stage)
+            if second_stage and (self.box_head is None or bank.q_half is None):
+                raise KeyError("state_dict has no roi_heads.box.* entries: the second stage was not packed")
+            if image_sizes is not None:
+                image_sizes = [tuple(s) for s in image_sizes for _ in range(table.classes)]
+            out = self.forward(images, None, concurrent, None, classes, bank, table)
+            h, w = images.shape[-2:]
+            pre = spec.PRE_NMS_TOP_N_TRAIN if training else spec.PRE_NMS_TOP_N_TEST
+            post = spec.POST_NMS_TOP_N_TRAIN if training else spec.POST_NMS_TOP_N_TEST
+            out["proposals"] = run_proposals(out["head"], h, w, pre, post, spec.NMS_THRESH, cuda_nms, image_sizes=image_sizes)
+            if second_stage:
+                out["detections"] = self.box_detect(out["features"], None, None, out["proposals"][0], out["proposals"][2], h, w,
+                                                    cuda_nms=cuda_nms, image_sizes=image_sizes, bank=bank, class_ids=table)
+            return out
+        if class_ids is not None:
+            raise ValueError("class_ids picks slots of a QueryBank: give bank= instead of queries")
         if isinstance(queries, ops.PackedImages):
             query_sizes = queries.image_sizes
         if isinstance(queries, ImageList):
@@ -516,13 +703,25 @@ class HotPathEngine(object):
         return out
 
     def box_detect(self, feats, qfeats, q_size, boxes, counts, img_h, img_w, shots=1, cuda_nms=True, want_raw=False,
-                   image_sizes=None, classes=1):
+                   image_sizes=None, classes=1, bank=None, class_ids=None):
         """roi_heads.box on given proposals (boxes [N,R,4] fp32, counts [N] int32 or None).  q_size: (h, w) of all queries
         or a list with every query's true size; image_sizes: true (h, w) per image of a padded batch.
-        classes = K (the class sweep): boxes / counts / image_sizes have N = B*K rows (b*K + k), feats B images, qfeats N*shots."""
+        classes = K (the class sweep): boxes / counts / image_sizes have N = B*K rows (b*K + k), feats B images, qfeats N*shots.
+        bank / class_ids (the query gallery, qfeats = q_size = None): N = B*K rows for the table's K, the query halves come from
+        the bank through the table and shots is the bank's."""
         if self.box_head is None:
             raise KeyError("state_dict has no roi_heads.box.* entries: the second stage was not packed")
         from .box_head import run_box_head
+        if bank is not None or qfeats is None:
+            batch = feats[0].shape[0]
+            table = self._bank_table(batch, qfeats, bank, class_ids, classes, True)
+            if bank.q_half is None:
+                raise KeyError("the QueryBank was enrolled without a packed second stage")
+            if batch * table.classes != boxes.shape[0]:
+                raise ValueError("%d rows of proposals are not images x slots = %d x %d" % (boxes.shape[0], batch, table.classes))
+            hw_dev = None if image_sizes is None else image_sizes_dev(image_sizes, boxes.device)
+            return run_box_head(self.box_head, feats, None, None, boxes, counts, img_h, img_w, shots=bank.shots, cuda_nms=cuda_nms,
+                                want_raw=want_raw, img_hw=hw_dev, classes=table.classes, bank=bank, slots=table.dev)
         hw_dev = None if image_sizes is None else image_sizes_dev(image_sizes, boxes.device)
         if classes != 1 and feats[0].shape[0] * classes != boxes.shape[0]:
             raise ValueError("%d rows of proposals are not images x classes = %d x %d" % (boxes.shape[0], feats[0].shape[0], classes))
@@ -535,12 +734,24 @@ class GraphedDetect(object):
     ~250 kernel launches per step cost one graph launch on the host, and the multi-stream fork/join of
     HotPathEngine.forward becomes parallel branches of the graph."""
 
-    def __init__(self, engine, images, queries, warmup=2, **kw):
+    def __init__(self, engine, images, queries=None, warmup=2, **kw):
         self.engine = engine
         self.images = images.clone()
-        self.queries = queries.clone()
-        # classes: a sweep's head and box head run at B*K rows, and those are the shapes to tune
-        engine.tune(self.images, self.queries, second_stage=bool(kw.get("second_stage")), classes=kw.get("classes", 1))
+        self.bank = kw.get("bank")
+        if self.bank is not None or queries is None:
+            # the query gallery: the slot table is a static device buffer of this graph; __call__ rewrites it (device to device, from
+            # the content cache) before a replay, so ONE captured graph serves changing per-image category lists
+            table = engine._bank_table(images.shape[0], queries, self.bank, kw.get("class_ids"), kw.get("classes", 1),
+                                       bool(kw.get("second_stage")))
+            self.slots = table.dev.clone()
+            self.table = SlotTable(table.classes, table.ids, self.slots)
+            self.queries = None
+            kw = dict(kw, class_ids=self.table)
+            engine.tune(self.images, None, second_stage=bool(kw.get("second_stage")), bank=self.bank, class_ids=self.table)
+        else:
+            self.queries = queries.clone()
+            # classes: a sweep's head and box head run at B*K rows, and those are the shapes to tune
+            engine.tune(self.images, self.queries, second_stage=bool(kw.get("second_stage")), classes=kw.get("classes", 1))
         side = torch.cuda.Stream(device=engine.device)
         side.wait_stream(_streams.current())
         with _streams.on(side):
@@ -552,10 +763,21 @@ class GraphedDetect(object):
         with torch.cuda.graph(self.graph):
             self.out = engine.detect(self.images, self.queries, **kw)
 
-    def __call__(self, images=None, queries=None):
+    def __call__(self, images=None, queries=None, class_ids=None):
+        if class_ids is not None:
+            if self.bank is None:
+                raise ValueError("class_ids picks slots of a QueryBank: this graph was captured with queries")
+            k, flat = check_class_ids(self.engine, self.bank, self.images.shape[0], class_ids)      # on the host, before anything moves
+            if k != self.table.classes:
+                raise ValueError("class_ids asks for %d slots per image; the graph was captured with %d" % (k, self.table.classes))
+            self.slots.copy_(slot_table_dev(flat, self.engine.device), non_blocking=True)
+            self.table.ids = [list(flat[b * k:(b + 1) * k]) for b in range(self.images.shape[0])]
+            self.out["class_ids"] = self.table.ids
         if images is not None:
             self.images.copy_(images, non_blocking=True)
         if queries is not None:
+            if self.queries is None:
+                raise ValueError("this graph was captured with a QueryBank: it takes no queries")
             self.queries.copy_(queries, non_blocking=True)
         self.graph.replay()
         return self.out

@@ -210,7 +210,9 @@ class OneShotDetector(nn.Module):
     `roi_heads.box.*` entries when present) under the reference's names, forward -> list[BoxList] with `scores` and
     `labels` (= target_ids[i]) like the reference returns.  target_ids[i] may be a sequence of K ids (the same K for every image):
     the class sweep, images_supp then holds B*K*S images (row (b*K + k)*S + s) and the result is ONE BoxList per image with the
-    detections of all K categories (merge_class_detections).  The options (spec.MODEL_OPTIONS) are model.HotPathEngine's and go to
+    detections of all K categories (merge_class_detections).  images_supp may be a model.QueryBank from `enroll` (the query gallery:
+    the supports were enrolled once); nested target_ids[i] are then labels of the bank (None: all of them, in the bank's order), and
+    the result is again one merged BoxList per image.  The options (spec.MODEL_OPTIONS) are model.HotPathEngine's and go to
     it as they are: which model the state_dict is of (siamese_backbone=False: no `supp_backbone`, the query goes through
     `backbone`) and how it was trained."""
 
@@ -224,11 +226,29 @@ class OneShotDetector(nn.Module):
     def state_dict(self, *a, **k):
         return dict(self.engine.sd)
 
+    def enroll(self, images_supp, labels, shots=1):
+        """The supports of a gallery, once: images_supp = G*shots images (row g*shots + s), labels = one distinct label per slot
+        -> model.QueryBank to pass as `images_supp` of forward (HotPathEngine.enroll)."""
+        images_supp = layers.to_image_list(images_supp)
+        qs = layers.ImageList(images_supp.tensors.to(self.engine.device, torch.float32), images_supp.image_sizes)
+        with torch.no_grad():
+            return self.engine.enroll(qs, shots=shots, labels=labels)
+
     def forward(self, images, images_supp, targets=None, device=None, target_ids=None):
         images = layers.to_image_list(images)
-        images_supp = layers.to_image_list(images_supp)
         dev = self.engine.device
         imgs = layers.ImageList(images.tensors.to(dev, torch.float32), images.image_sizes)
+        if isinstance(images_supp, model.QueryBank):
+            bank = images_supp
+            class_ids = bank.slots_of(target_ids, imgs.tensors.shape[0])      # ValueError for a label the bank does not hold
+            if bank.labels is None:
+                raise ValueError("this QueryBank was enrolled without labels: the detections could not be labelled")
+            with torch.no_grad():
+                out = self.engine.detect(imgs, bank=bank, class_ids=class_ids, second_stage=self.second_stage)
+            labels = [[bank.labels[i] for i in row] for row in out["class_ids"]]
+            b, s, c = (out["detections"][k] for k in ("boxes", "scores", "counts")) if self.second_stage else out["proposals"]
+            return merge_class_detections(b, s, c, labels, imgs.image_sizes)
+        images_supp = layers.to_image_list(images_supp)
         qs = layers.ImageList(images_supp.tensors.to(dev, torch.float32), images_supp.image_sizes)
         if target_ids is not None and len(target_ids) and isinstance(target_ids[0], (list, tuple)):
             classes = len(target_ids[0])

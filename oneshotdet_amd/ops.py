@@ -618,6 +618,33 @@ def correlate_levels_sweep(xs, qs, classes):
     return ys
 
 
+def correlate_levels_gallery(xs, qs, slots, classes):
+    """The query gallery's correlation (include/oneshotdet_hip_gallery.h): xs = NHWC level maps [n, H_l, W_l, C], qs = [G, C] fp32 per
+    level (the enrolled gallery), slots = device int32 [n*classes] of gallery rows -> [n*classes, H_l, W_l, C] per level, row
+    b*classes + k = xs[b] * qs[slots[b*classes + k]], in ONE launch.  The bits of correlate_levels_sweep on the gathered vectors
+    qs[slots]; nothing is gathered.  The table is validated on the host by its maker (model.check_class_ids): a slot outside
+    [0, G) read on the device gives a NaN row."""
+    _chk_dev(slots, *xs)
+    k = len(xs)
+    n, c = xs[0].shape[0], xs[0].shape[-1]
+    classes = int(classes)
+    if classes < 1:
+        raise ValueError("classes must be at least 1, got %d" % classes)
+    g = qs[0].shape[0]
+    assert all(x.shape[0] == n and x.shape[-1] == c and x.is_contiguous() for x in xs)
+    assert all(q.shape == (g, c) and q.dtype == torch.float32 and q.is_contiguous() for q in qs)
+    assert slots.dtype == torch.int32 and slots.shape == (n * classes,) and slots.is_contiguous()
+    ys = [torch.empty((n * classes,) + tuple(x.shape[1:]), device=x.device, dtype=x.dtype) for x in xs]
+    if n == 0:              # an empty table has no address to pass
+        return ys
+    hws = (C.c_int32 * k)(*[x.shape[1] * x.shape[2] for x in xs])
+    _lib.call("osd_correlate_levels_gallery", k, _ptr_array(xs), _ptr_array(qs), _p(slots), _ptr_array(ys), hws, n, classes, g, c,
+              _dt(xs[0]), _stream())
+    for x, q, y in zip(xs, qs, ys):
+        _rec("correlate_gallery", x=x, q=q, slots=slots, out=y, classes=classes)
+    return ys
+
+
 def class_sweep_group():
     """Query vectors per workgroup of correlate_levels_sweep (OSD_CLASS_SWEEP_GROUP of the built library)."""
     return int(_lib.load().osd_class_sweep_group())
@@ -1323,14 +1350,25 @@ def roi_pool_levels(feats, scales, boxes, counts, pool, sampling_ratio, out=None
 
 
 def groupnorm_act_rois(x, gamma, beta, groups=32, eps=1e-5, slope=0.2, addend=None, rois_per_add=1, add_stride=1,
-                       add_offset=0, out=None):
-    """LeakyReLU(slope)(GroupNorm(groups, C)(x [+ addend map of the ROI's image / shot])) on [R,7,7,C] ROI maps."""
-    _chk_dev(x, gamma, beta, addend)
+                       add_offset=0, out=None, add_index=None):
+    """LeakyReLU(slope)(GroupNorm(groups, C)(x [+ addend map of the ROI's image / shot])) on [R,7,7,C] ROI maps.
+    add_index (the query gallery, include/oneshotdet_hip_gallery.h): device int32, one entry per ROI set of rois_per_add samples; the
+    addend row of sample i is add_index[i // rois_per_add] * add_stride + add_offset instead of (i // rois_per_add) * add_stride +
+    add_offset.  The bits of the plain call on the gathered addend."""
+    _chk_dev(x, gamma, beta, addend, add_index)
     r, h, w, c = x.shape
     if out is None:
         out = torch.empty_like(x)
     if addend is not None:
         assert addend.dtype == x.dtype and addend.shape[1:] == x.shape[1:] and addend.is_contiguous()
+    if add_index is not None:
+        if addend is None:
+            raise ValueError("add_index picks rows of an addend: none given")
+        assert add_index.dtype == torch.int32 and add_index.is_contiguous() and add_index.numel() * rois_per_add >= r
+        _lib.call("osd_groupnorm_act_rois_gallery", _p(x), _p(addend), _p(add_index), _p(gamma), _p(beta), _p(out), r, h * w, c,
+                  groups, float(eps), float(slope), rois_per_add, add_stride, add_offset, addend.shape[0], _dt(x), _stream())
+        _rec("groupnorm_act_rois_gallery", x=x, addend=addend, add_index=add_index, out=out)
+        return out
     _lib.call("osd_groupnorm_act_rois", _p(x), _p(addend), _p(gamma), _p(beta), _p(out), r, h * w, c, groups,
               float(eps), float(slope), rois_per_add, add_stride, add_offset, _dt(x), _stream())
     return out
