@@ -170,6 +170,14 @@ SIGNATURES_GALLERY = {
     "osd_groupnorm_act_rois_gallery": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i, _f, _f, _i, _i, _i, _i, _i, _p]),
 }
 
+# include/oneshotdet_hip_pred_bwd.h: the prediction convs' fused backward launch (data + weight gradient, no gathered dy in
+# memory), an eighth table
+PRED_BWD_BOTH, PRED_BWD_DGRAD, PRED_BWD_WGRAD = 0, 1, 2
+SIGNATURES_PRED_BWD = {
+    "osd_pred_bwd_workspace_bytes": (_i64, [_i, _p, _p, _p, _i, _i]),
+    "osd_conv2d_pred_bwd": (_i, [C.POINTER(ConvDesc), _i, _p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i, _p]),
+}
+
 _lib = None
 
 
@@ -190,7 +198,8 @@ def load():
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in (list(SIGNATURES.items()) + list(SIGNATURES_BOX_MODES.items()) + list(SIGNATURES_SOFT_LABELS.items())
                               + list(SIGNATURES_NEG_SUPPORT.items()) + list(SIGNATURES_SOLVER.items())
-                              + list(SIGNATURES_CLASS_SWEEP.items()) + list(SIGNATURES_GALLERY.items())):
+                              + list(SIGNATURES_CLASS_SWEEP.items()) + list(SIGNATURES_GALLERY.items())
+                              + list(SIGNATURES_PRED_BWD.items())):
         fn = getattr(lib, name)   # AttributeError if the symbol is missing
         fn.restype = res
         fn.argtypes = args

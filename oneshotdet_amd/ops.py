@@ -23,6 +23,7 @@ def _stream():
 
 
 from .trace import rec as _rec      # launch trace (tests only): oneshotdet_amd/trace.py
+from . import trace as _trace
 
 
 def _dt(t):
@@ -884,6 +885,55 @@ def pred_dgrad_pack(w_master, cout, cin, dtype, out=None):
     _lib.call("osd_pred_dgrad_pack", _dt(wd), _p(w_master), cout, cin, _p(wd), _stream())
     _rec("pred_dgrad_pack", w=w_master, cout=cout, cin=cin, out=wd)
     return wd
+
+
+def pred_bwd_fused_ok(dtype, cout, r, s, stride, pad, cin, n_levels):
+    """Does the prediction convs' fused backward launch (osd_conv2d_pred_bwd) cover this conv?  bf16 + the gate of pred_gemm_ok."""
+    return dtype == torch.bfloat16 and pred_gemm_ok(cout, r, s, stride, pad, cin, n_levels)
+
+
+def pred_bwd_fused(xs, dys, wd_ent, dw, db, cout, flags=_lib.PRED_BWD_BOTH):
+    """Backward of a prediction conv over the levels (xs[l] NHWC input, dys[l] NHWC with >= 4 channels stored) as ONE launch + its
+    reduce: dw [cout][3][3][cin] / db [cout] fp32 are added to; -> the per-level dX, views of one buffer [sum n h w][cin] (the rows
+    in pred_dy_gather's order).  wd_ent: the PackedConv of pred_dgrad_pack's matrix.  The gathered matrix G is not written to memory.
+    flags: PRED_BWD_DGRAD / PRED_BWD_WGRAD run one half (-> None for the weight-gradient half).
+    Under a launch trace the call is recorded as the launches it replaces: G is built (pred_dy_gather records itself), the data gradient
+    is the `conv` record of the 1x1 conv over that G whose output is this launch's buffer, the weight gradient a `wgrad` record."""
+    x0, dy0 = xs[0], dys[0]
+    _chk_dev(x0, dy0, dw)
+    cin = x0.shape[-1]
+    d = _conv_desc(x0.shape, _dt(x0), cout, 3, 3, 1, 1, dy0.shape[-1])
+    k = len(xs)
+    tot = sum(t.shape[0] * t.shape[1] * t.shape[2] for t in dys)
+    dg, wg = flags != _lib.PRED_BWD_WGRAD, flags != _lib.PRED_BWD_DGRAD
+    xp = (C.c_void_p * k)(*[t.data_ptr() for t in xs])
+    dyp = (C.c_void_p * k)(*[t.data_ptr() for t in dys])
+    ns = (C.c_int32 * k)(*[t.shape[0] for t in dys])
+    hs = (C.c_int32 * k)(*[t.shape[1] for t in dys])
+    ws = (C.c_int32 * k)(*[t.shape[2] for t in dys])
+    dx = torch.empty((tot, cin), device=x0.device, dtype=x0.dtype) if dg else None
+    wsp = None
+    if wg:
+        need = int(_lib.load().osd_pred_bwd_workspace_bytes(k, ns, hs, ws, cin, cout))
+        wsp = torch.empty((need // 4 + 1,), device=x0.device, dtype=torch.float32)
+    _lib.call("osd_conv2d_pred_bwd", C.byref(d), k, xp, dyp, ns, hs, ws, _p(wd_ent.w) if dg else None, _p(dx), _p(dw) if wg else None,
+              _p(db) if wg else None, _p(wsp), flags, _stream())
+    if wg:
+        _rec("wgrad", items=[dict(x=x, dy=dy, dw=dw, scale=None, db=db, r=3, s=3, stride=1, pad=1, cout=cout) for x, dy in zip(xs, dys)],
+             algo="pred", key=None)
+    if not dg:
+        return None
+    if _trace.TRACE is not None and not _TUNING[0]:
+        g = pred_dy_gather(dys, cout, cin)
+        _rec("conv", x=g.view(1, 1, tot, PRED_G), w=wd_ent.w, bias=wd_ent.bias, cout=wd_ent.cout_store, r=1, s=1, stem=False, stride=1,
+             pad=0, act=ACT_NONE, res=None, res_mode=RES_NONE, relu_in=False, act_scale=1.0, act_scale_dev=None, mask=None,
+             out=dx.view(1, 1, tot, cin), algo="pred_bwd", key=None)
+    out, q0 = [], 0
+    for t in dys:
+        n, hh, ww = t.shape[0], t.shape[1], t.shape[2]
+        out.append(dx[q0:q0 + n * hh * ww].view(n, hh, ww, cin))
+        q0 += n * hh * ww
+    return out
 
 
 def conv2d_wgrad_grouped(pairs, dw_packed, r, s, stride, pad, cout, scale=None, db=None, algo=None, g=None):

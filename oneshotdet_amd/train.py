@@ -193,6 +193,9 @@ class TrainEngine(ForwardPass, BackwardPass, SecondStage, Update, State):
         # OSD_NO_PRED_DGRAD_GEMM=1: the 3x3 conv over dy, A/B)
         self.pred_dgrad_gemm = os.environ.get("OSD_NO_PRED_DGRAD_GEMM", "0") == "0"
         self._pred_dgrad = {}
+        # bf16: gather, both GEMMs and the scatter of a prediction conv's backward as one launch that keeps G in LDS
+        # (ops.pred_bwd_fused; OSD_PRED_BWD_FUSED=0: the gathered path above, A/B)
+        self.pred_bwd_fused = os.environ.get("OSD_PRED_BWD_FUSED", "1") != "0"
         # experiment (train_backward._release_held_wgrads): "" = the towers' weight gradients go out where the head backward ends
         self.tower_wgrad_at = os.environ.get("OSD_TOWER_WGRAD_AT", "")
         self._held_wgrads = []

@@ -105,6 +105,13 @@ class BackwardPass(object):
         that writes all levels (round 5; until then a 3x3 conv over dy with its 2 / 4 input channels padded to 64 per tap:
         118 - 132 us on the critical chain for a 70 MB write).  -> the per-level d(t_last), views of one buffer."""
         nl = len(dpred)
+        if self.pred_bwd_fused and ops.pred_bwd_fused_ok(self.dtype, c.cout, c.r, c.s, 1, c.r // 2, c.cin, nl):
+            # bf16: ONE launch on this chain's stream builds G tile by tile in LDS and gives both gradients (+ a small reduce of
+            # the per-workgroup weight-gradient partials): t_last is read once, d(t_last) written once, G never reaches memory.
+            # The weight gradient is written on the CHAIN stream, not the side stream: the head bucket's update waits for the main
+            # stream, which has joined both towers' chains by then (head_backward; _bucket_ready("head", ...) lists it)
+            ent = self.pred_dgrad_weights(c, fresh_ok=True)
+            return ops.pred_bwd_fused(t_last, dpred, ent, c.gw, c.gb if c.has_bias else None, c.cout)
         g = ops.pred_dy_gather(dpred, c.cout, c.cin)
         self._wgrad_grouped(c, [(t_last[l], dpred[l]) for l in range(nl)], which, g=g)
         ent = self.pred_dgrad_weights(c, fresh_ok=True)
