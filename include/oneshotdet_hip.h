@@ -255,6 +255,46 @@ int osd_correlate_levels(int n_levels, const void* const* xs, const float* const
                          int n, int c, int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * The correlation for K category slots per target image.  The class sweep: K category slots (support sets) per target
+ * image in one pass.  The target pyramid is computed once per image; the two places where it enters the per-(image,
+ * category) work read ONE pyramid from K rows (osd_correlate_levels_sweep here, osd_roi_pool_levels_sweep in the box head).
+ * The query gallery: the supports of G gallery slots are enrolled once (pooled query vectors, query halves of the box head's
+ * first conv); every later call detects its images against rows of that bank, picked per (image, category slot) by a table of
+ * slot numbers in device memory.  The two places where the enrolled data enters the per-(image, category) work read it
+ * THROUGH the table (osd_correlate_levels_gallery here, osd_groupnorm_act_rois_gallery in the box head), so nothing is
+ * gathered, copied or recomputed per call.
+ * ---------------------------------------------------------------------------------------------------------------- */
+/* Query vectors a workgroup of osd_correlate_levels_sweep stages in LDS, and products it stores per 16-byte load of x. */
+#define OSD_CLASS_SWEEP_GROUP 8
+
+/* OSD_CLASS_SWEEP_GROUP, from the built library (the binding and the tests read it here). */
+int osd_class_sweep_group(void);
+
+/* modeling/detector/generalized_rcnn.py:307-311 run `classes` times on the same image, in one launch for all levels:
+ *   xs[l] [n][hw_l][c] (dtype), qs[l] [n*classes][c] fp32, ys[l] [n*classes][hw_l][c] (dtype),
+ *   ys[l][b*classes + k] = xs[l][b] * qs[l][b*classes + k]   (broadcast over the pixels)
+ * A workgroup stages up to OSD_CLASS_SWEEP_GROUP query vectors of its image in LDS, loads each 16-byte chunk of x once and stores
+ * one product per staged vector; the last group of an image is short when `classes` is no multiple of the group.  Per element
+ * the arithmetic is osd_correlate_levels' (fp32 product, then the store conversion): the same bits as that entry on `classes`
+ * times replicated xs, and with classes == 1 its result.  Levels with hws[l] <= 0 are skipped.  Channel rule as
+ * osd_correlate_levels.  OSD_ERR_INVALID_ARG for null arrays or tensors, n < 0, classes < 1, a bad channel count or dtype; nothing
+ * is launched then.  n == 0 is a no-op. */
+int osd_correlate_levels_sweep(int n_levels, const void* const* xs, const float* const* qs, void* const* ys, const int32_t* hws,
+                               int n, int classes, int c, int dtype, void* stream);
+
+/* modeling/detector/generalized_rcnn.py:307-311 for `classes` category slots per image, the query vectors taken from a gallery:
+ *   xs[l] [n][hw_l][c] (dtype), qs[l] [n_gallery][c] fp32, slots [n*classes] int32 (device), ys[l] [n*classes][hw_l][c] (dtype),
+ *   ys[l][b*classes + k] = xs[l][b] * qs[l][slots[b*classes + k]]   (broadcast over the pixels)
+ * osd_correlate_levels_sweep's walk (OSD_CLASS_SWEEP_GROUP vectors staged per workgroup, each 16-byte chunk of x loaded once, one
+ * store per staged vector, the same level table) with the staged vectors read through `slots`: the same bits as that entry on
+ * the gathered vectors qs[l][slots].  Slots may repeat and come in any order.  A slot outside [0, n_gallery) is never used as an
+ * address: its output row is NaN (the callers validate the table on the host; this is the device's own guard).  Levels with
+ * hws[l] <= 0 are skipped.  Channel rule as osd_correlate_levels.  OSD_ERR_INVALID_ARG for null arrays, tensors or slots, n < 0,
+ * classes < 1, n_gallery < 1, a bad channel count or dtype; nothing is launched then.  n == 0 is a no-op. */
+int osd_correlate_levels_gallery(int n_levels, const void* const* xs, const float* const* qs, const int32_t* slots, void* const* ys,
+                                 const int32_t* hws, int n, int classes, int n_gallery, int c, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Proposal pipeline (FCOSPostProcessor, modeling/rpn/fcos/inference.py:46-137,251-323) and NMS (_C.nms,
  * csrc/nms.h:10-28, csrc/cuda/nms.cu:23-131), batched over images, no host sync.
  * ---------------------------------------------------------------------------------------------------------------- */
@@ -383,6 +423,33 @@ int osd_pred_dy_gather(const osd_conv_desc* d, int n_seg, const void* const* dys
 int osd_pred_dgrad_pack(int dtype, const float* w, int cout, int cin, void* wd, void* stream);
 int osd_conv2d_wgrad_pred_gathered(const osd_conv_desc* d, int n_seg, const void* const* xs, const void* g, const int32_t* ns,
                                    const int32_t* hs, const int32_t* ws, float* dw, float* db, void* workspace, void* stream);
+/* The backward pass of an FCOS prediction conv (rpn/fcos/fcos.py:50-61,91-97: cls_logits + centerness, bbox_pred) as ONE launch
+ * over all FPN levels.  The gathered matrix G [pixels][64] of osd_pred_dy_gather is built tile by tile in LDS and never reaches
+ * memory: the launch reads x once and writes dx once. */
+/* `flags` of osd_conv2d_pred_bwd: both gradients, the data gradient only, the weight + bias gradient only */
+#define OSD_PRED_BWD_BOTH 0
+#define OSD_PRED_BWD_DGRAD 1
+#define OSD_PRED_BWD_WGRAD 2
+/* Bytes of the workspace osd_conv2d_pred_bwd needs for these levels (the per-workgroup partial weight gradients: 9 * cout rows of
+ * cin fp32 values per workgroup, no initialisation needed).  0 for arguments the launch refuses. */
+int64_t osd_pred_bwd_workspace_bytes(int n_seg, const int32_t* ns, const int32_t* hs, const int32_t* ws, int cin, int cout);
+/* Backward of a 3x3 / stride 1 / pad 1 conv with cout <= 4 and cin % 256 == 0 in bf16 over n_seg <= 6 levels (desc: dtype, cin,
+ * cout, r, s, stride, pad, out_stride = channels stored per dy pixel, a multiple of 4; n / h / w are taken from ns / hs / ws, HOST
+ * arrays):
+ *   xs[l]  [ns[l]][hs[l]][ws[l]][cin]         the conv's input (dense NHWC, 16-byte aligned)
+ *   dys[l] [ns[l]][hs[l]][ws[l]][out_stride]  the gradient of its output (8-byte aligned; channels >= cout are ignored)
+ *   wd_packed [cin][64]                       the weights as osd_pred_dgrad_pack writes them
+ *   dx [sum_l ns hs ws][cin]                  WRITTEN: the data gradient, the levels one after the other (rows in G's order), rounded
+ *                                             once from the fp32 sum over the 64 columns of G
+ *   dw [cout][3][3][cin] fp32, db [cout] fp32 ADDED TO (db may be null): the weight and bias gradient summed over the levels
+ * The weight gradient is accumulated per workgroup in registers over all its pixels, stored to `workspace` and added into dw / db
+ * by a second launch in workgroup order: no atomics, the same bits every run.  flags = OSD_PRED_BWD_DGRAD ignores xs, dw, db and
+ * workspace (they may be null); OSD_PRED_BWD_WGRAD ignores wd_packed and dx.  Either half computes the bits the fused launch does.
+ * OSD_ERR_UNSUPPORTED: fp32, another geometry, cout > 4, cin % 256 != 0, out_stride % 4 != 0.  OSD_ERR_INVALID_ARG: n_seg outside
+ * 1..6, a null or misaligned pointer the flags need, an empty level, bad flags or dtype.  Nothing is launched then. */
+int osd_conv2d_pred_bwd(const osd_conv_desc* desc, int n_seg, const void* const* xs, const void* const* dys, const int32_t* ns,
+                        const int32_t* hs, const int32_t* ws, const void* wd_packed, void* dx, float* dw, float* db, void* workspace,
+                        int flags, void* stream);
 /* n_seg <= 24 convs of IDENTICAL geometry (d: the shared forward descriptor incl. n, h, w) but different tensors AND
  * different weights — the repeated bottleneck blocks of a ResNet stage (resnet.py:295-315) — in one launch; xs / dys /
  * scales / dws / dbs: HOST arrays of per-conv device pointers (scales, dbs nullable as a whole or per entry).  The output
@@ -482,6 +549,38 @@ int osd_sgd_momentum_multi(const void* table, const int32_t* block_entry, int n_
 int osd_sgd_momentum_pack_multi(const void* table, const int32_t* block_entry, int n_blocks, float* params,
                                 float* grads, float* momentum_buf, const float* scales, void* packed, int dtype,
                                 float lr, float momentum, int first_step, int zero_grads, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * The optimiser update with its learning rate read from device memory, so that a captured update (hipGraph) follows a
+ * learning-rate schedule (solver/lr_scheduler.py:10-52, WarmupMultiStepLR) without being captured again.
+ *
+ * The solver block: 8 bytes of device memory, 8-byte aligned,
+ *   struct { float lr; int32_t first_step; }
+ * lr is the rate of the weight group (a table entry's lr_mult makes the bias group's, solver/build.py:8-26); first_step != 0: the
+ * momentum buffer is not read (buf = g), as with the by-value entries' first_step.
+ * ---------------------------------------------------------------------------------------------------------------- */
+/* Write the solver block: one workgroup, one lane, two plain stores.  Stream-ordered like any launch — the values travel as
+ * kernel arguments, so the caller keeps no staging buffer alive — and meant to run BETWEEN graph launches, never inside a captured
+ * graph (its arguments would be baked in like the by-value entries').  Exactly the block's 8 bytes are written.
+ * OSD_ERR_INVALID_ARG for a null block or one that is not 8-byte aligned; nothing is launched then. */
+int osd_solver_set(void* block, float lr, int first_step, void* stream);
+
+/* osd_sgd_momentum_multi with (lr, first_step) read from the solver block: every workgroup loads the block once (a wave-uniform
+ * load) and then runs the by-value entry's update — the same code, so the same bits for the same rate.  Arguments as
+ * osd_sgd_momentum_multi's, `float lr, ..., int first_step` replaced by `const void* solver_block`.  OSD_ERR_INVALID_ARG for a null
+ * or misaligned block; nothing is launched then. */
+int osd_sgd_momentum_multi_dev(const void* table, const int32_t* block_entry, int n_blocks, float* params, const float* grads,
+                               float* momentum_buf, const void* solver_block, float momentum, void* stream);
+
+/* osd_sgd_momentum_pack_multi with (lr, first_step) read from the solver block, as above. */
+int osd_sgd_momentum_pack_multi_dev(const void* table, const int32_t* block_entry, int n_blocks, float* params, float* grads,
+                                    float* momentum_buf, const float* scales, void* packed, int dtype,
+                                    const void* solver_block, float momentum, int zero_grads, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Backward pass, continued: GroupNorm + ReLU of the FCOS towers over all FPN levels (forward and backward) and the FCOS
+ * loss.
+ * ---------------------------------------------------------------------------------------------------------------- */
 /* GroupNorm + ReLU of one tower layer over ALL FPN levels (separate tensors sharing gamma/beta) in two launches, and
  * its backward in two launches: statistics per (level, image, slab), finalised inside the apply kernels.
  * xs/ys/us/dts/dus: HOST arrays of n_levels device pointers to [n][hw_l][c] tensors; hws: HOST array;
@@ -632,6 +731,33 @@ int osd_append_gt_boxes(const float* boxes, const float* scores, const int32_t* 
                         int max_gt, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * The box head for K category slots per target image: the ROI pooling of the class sweep and the ROI GroupNorm of the
+ * query gallery (see the correlation section for both).
+ * ---------------------------------------------------------------------------------------------------------------- */
+/* modeling/poolers.py:93-124 run for `sets_per_image` ROI sets on the same image: osd_roi_pool_levels with level maps
+ * xs[l] [n_sets / sets_per_image][h_l][w_l][c]; ROI set j (boxes [n_sets][max_rois][4], counts [n_sets] or null) reads image
+ * j / sets_per_image.  y, y_stride and level_out as osd_roi_pool_levels.  The same device code as that entry, so the same bits as
+ * that entry on replicated maps.  OSD_ERR_INVALID_ARG as osd_roi_pool_levels, and for sets_per_image < 1 or
+ * n_sets % sets_per_image != 0; nothing is launched then. */
+int osd_roi_pool_levels_sweep(int n_levels, const void* const* xs, const int32_t* hs, const int32_t* ws, const float* scales,
+                              const float* boxes, const int32_t* counts, void* y, int n_sets, int sets_per_image, int c,
+                              int max_rois, int pool, int sampling_ratio, int y_stride, int32_t* level_out, int dtype,
+                              void* stream);
+
+/* modeling/roi_heads/box_head/box_head.py:43-66,146-148: osd_groupnorm_act_rois with the addend row of sample i taken through a
+ * table, addend [n_add][hw][c] (dtype), add_index [ceil(n_samples / rois_per_add)] int32 (device):
+ *   row(i) = add_index[i / rois_per_add] * add_stride + add_offset
+ * (add_stride = shots of a gallery slot, add_offset = the shot).  The same device code as that entry, so the same bits as that
+ * entry on the gathered addend.  A row outside [0, n_add) is never used as an address: the sample's output is NaN.  Shapes as
+ * osd_groupnorm_act_rois, and at most 65535 ROI sets: the launch is a 2-D grid (ROI within its set, set), so a workgroup finds its
+ * table entry without a division (OSD_ERR_UNSUPPORTED otherwise).  OSD_ERR_INVALID_ARG for a null x, addend, add_index, gamma, beta or y,
+ * n_samples < 0, rois_per_add < 1, add_stride < 1, add_offset < 0, n_add < 1 or a bad dtype; nothing is launched then.
+ * n_samples == 0 is a no-op. */
+int osd_groupnorm_act_rois_gallery(const void* x, const void* addend, const int32_t* add_index, const float* gamma, const float* beta,
+                                   void* y, int n_samples, int hw, int c, int groups, float eps, float slope, int rois_per_add,
+                                   int add_stride, int add_offset, int n_add, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Second stage, TRAINING path: FastRCNNLossComputation (modeling/roi_heads/box_head/loss.py).
  * ---------------------------------------------------------------------------------------------------------------- */
 /* subsample (loss.py:234-301): per image match the proposals (boxes [n][max_props][4], counts [n]; the ground truth already
@@ -675,6 +801,36 @@ int osd_rois_sum(const void* x, void* out, int n, int rois_per_image, int64_t el
 int osd_roi_pool_levels_bwd(int n_levels, float* const* gxs, const int32_t* hs, const int32_t* ws, const float* scales,
                             const float* boxes, const int32_t* counts, const void* dy, int n, int c, int max_rois, int pool,
                             int sampling_ratio, int dy_stride, int dtype, void* stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
+ * Second stage: the negative support (FEW_SHOT.NEG_SUPPORT.TURN_ON with SECOND_STAGE_METHOD 'concat' and
+ * SECOND_STAGE_CLS_LOSS 'ce_loss', config/defaults.py).
+ *
+ * The box head scores the sampled ROIs twice with the same weights (modeling/roi_heads/box_head/box_head.py:128-139): against the
+ * support crop of the queried category (pred) and against a crop of another category (pred_neg).  Both are rows of 2 class logits
+ * followed by the 2 x 4 box deltas; the deltas of pred_neg are never read (box_head.py: neg_box_regression is unused).
+ * ---------------------------------------------------------------------------------------------------------------- */
+/* FastRCNNLossComputation.__call__ with a negative support (loss.py:359,379-393,435-444, gt_label == -1), the weights of
+ * box_head.py:180-188 folded in.  osd_box_loss's arguments, with the same meaning, plus pred_neg [n*rois_per_image][pred_stride] (the
+ * dtype of pred; required), d_pred_neg [n*rois_per_image][grad_stride] (given exactly when d_pred is), margin (0.3 in the reference)
+ * and w_suppress (2.5).  OSD_ERR_INVALID_ARG for a null pred_neg, for one of d_pred / d_pred_neg without the other, or for
+ * pred_stride (grad_stride, when the gradients are given) below 2 + 8.
+ *   losses[5] = {w_cls * cross-entropy, w_box * smooth-L1, M, w_suppress * suppress, K}
+ * M = the valid rows (the first min(s_count[image], rois_per_image) of every image), K = the valid rows with label 1, and
+ *   suppress = (1 / K) sum over those K rows of relu(q - p + margin),  p = softmax(pred row)[1], q = softmax(pred_neg row)[1].
+ * Gradients: d_pred[r][0:2] = the cross-entropy's plus the hinge's, (w_suppress / K) p (1 - p) * (+1, -1) where q - p + margin > 0;
+ * d_pred[r][2:10] as osd_box_loss; d_pred_neg[r][0:2] = (w_suppress / K) q (1 - q) * (-1, +1) where the hinge is active.  Every other
+ * element of the grad_stride columns of d_pred_neg is written 0: the delta columns, and the whole row where it is past
+ * s_count[image], background, or has q - p + margin <= 0.  With d_pred == NULL only the losses are computed.
+ * K == 0: suppress = 0 and no hinge gradient.  (The reference takes the mean of an empty tensor, NaN, there; its matcher and the
+ * appended ground-truth proposals keep a real step from reaching that state.  Zero is this kernel's documented answer.)
+ * Rows past s_count[image] are never read.  A label > 1 has no columns in the row: losses[0], [1] and [3] come back NaN.  With
+ * w_suppress == 0 losses[0..2] and d_pred are osd_box_loss's bit for bit.  One workgroup, any M, fixed summation order, no
+ * floating-point atomics. */
+int osd_box_loss_neg_support(const void* pred, const void* pred_neg, const int32_t* labels, const float* targets,
+                             const int32_t* s_count, int n, int rois_per_image, int pred_stride, float w_cls, float w_box,
+                             float margin, float w_suppress, float* losses, void* d_pred, void* d_pred_neg, int grad_stride,
+                             int dtype, void* stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Input transforms (data/transforms/transforms.py:27-92 in the Compose order of

@@ -16,6 +16,9 @@ LIB = os.path.join(LIBDIR, "liboneshotdet_hip%s.so" % ("_" + TAG if TAG else "")
 SOURCES = ["osd_error.hip", "conv_igemm.hip", "conv_igemm_dma.hip", "conv_igemm_sp.hip", "conv_pred.hip", "conv_pred_bwd.hip", "conv_px.hip", "conv_wgrad.hip", "conv_wgrad_sk.hip", "backward.hip", "groupnorm_onepass.hip", "loss.hip", "elementwise.hip", "proposals.hip", "box_head.hip", "transforms.hip", "box_train.hip", "evaluation.hip", "query_avgpool.hip", "class_sweep.hip", "gallery.hip"]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wno-unused-result"] + os.environ.get("OSD_BUILD_FLAGS", "").split()
+INCLUDE = os.path.join(os.path.dirname(HERE), "include")
+# every header under csrc/ and include/ is a dependency of every object (a handful of small files: a finer map is not worth a stale build)
+HEADERS = sorted(os.path.join(d, f) for d in (CSRC, INCLUDE) for f in os.listdir(d) if f.endswith(".h"))
 
 
 def _stale(target, deps):
@@ -29,8 +32,6 @@ def build_library(force=False, verbose=True):
     os.makedirs(LIBDIR, exist_ok=True)
     objdir = os.path.join(LIBDIR, "obj" + ("_" + TAG if TAG else ""))
     os.makedirs(objdir, exist_ok=True)
-    # every header under csrc/ is a dependency of every object (a handful of small files: a finer map is not worth a stale build)
-    headers = sorted(os.path.join(CSRC, f) for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join(os.path.dirname(HERE), "include", h) for h in ("oneshotdet_hip.h", "oneshotdet_hip_box_modes.h", "oneshotdet_hip_soft_labels.h", "oneshotdet_hip_neg_support.h", "oneshotdet_hip_solver.h", "oneshotdet_hip_class_sweep.h", "oneshotdet_hip_gallery.h", "oneshotdet_hip_pred_bwd.h")]
     # objects of sources that are no longer built (retired kernels) do not stay behind: nothing links them, but they travel with
     # the snapshot and read as live code
     keep = set(src.replace(".hip", ".o") for src in SOURCES)
@@ -42,7 +43,7 @@ def build_library(force=False, verbose=True):
         s = os.path.join(CSRC, src)
         o = os.path.join(objdir, src.replace(".hip", ".o"))
         objs.append(o)
-        if force or _stale(o, [s] + headers):
+        if force or _stale(o, [s] + HEADERS):
             cmd = [HIPCC] + FLAGS + ["-c", s, "-o", o]
             if verbose:
                 print(" ".join(cmd), flush=True)

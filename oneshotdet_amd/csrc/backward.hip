@@ -222,11 +222,11 @@ __device__ __forceinline__ float sgd_update(float w, float g, float b, float wd,
   return __builtin_fmaf(-step, m, w);
 }
 
-// The solver block of include/oneshotdet_hip_solver.h: the rate and the first-step flag in device memory, for an update inside a
+// The solver block of include/oneshotdet_hip.h: the rate and the first-step flag in device memory, for an update inside a
 // captured graph.  The `_dev` kernels below load it once per workgroup (through a const __restrict__ kernel argument: a
 // wave-uniform load) and run the SAME body as the by-value kernels, which take the two values as kernel arguments.
 struct alignas(8) SolverBlock { float lr; int first_step; };
-static_assert(sizeof(SolverBlock) == 8, "solver block layout (oneshotdet_hip_solver.h)");
+static_assert(sizeof(SolverBlock) == 8, "solver block layout (oneshotdet_hip.h)");
 
 __global__ void __launch_bounds__(64) solver_set_kernel(SolverBlock* __restrict__ block, float lr, int first_step) {
   if (blockIdx.x == 0 && threadIdx.x == 0) { block->lr = lr; block->first_step = first_step; }
@@ -746,7 +746,7 @@ extern "C" int osd_sgd_momentum_pack_multi(const void* table, const int32_t* blo
   return osd_check_launch("sgd_pack_multi");
 }
 
-// include/oneshotdet_hip_solver.h: the rate and the first-step flag from the 8-byte solver block
+// include/oneshotdet_hip.h: the rate and the first-step flag from the 8-byte solver block
 static int solver_block_ok(const void* block, const char* who) {
   if (!block) return osd_fail(OSD_ERR_INVALID_ARG, "%s: null solver block", who);
   if (reinterpret_cast<uintptr_t>(block) & 7) return osd_fail(OSD_ERR_INVALID_ARG, "%s: the solver block %p is not 8-byte aligned", who, block);

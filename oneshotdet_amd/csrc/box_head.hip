@@ -7,7 +7,6 @@
 #include "osd_common.h"
 #include "gn_act_rois.h"
 #include "../../include/oneshotdet_hip_box_modes.h"
-#include "../../include/oneshotdet_hip_class_sweep.h"
 
 namespace {
 
@@ -70,7 +69,7 @@ __device__ __forceinline__ int map_level(float x1, float y1, float x2, float y2,
 // 5 % slower end to end, 996 vs 1045 images/s: the vector L1 already serves the repeated taps, and the staged version
 // pays a barrier, an LDS round trip and 4x the workgroups.)
 // `sets_per_image`: ROI set (boxes / counts row) j reads image j / sets_per_image of the level maps — 1 for the per-pair entry, the
-// class sweep's K for osd_roi_pool_levels_sweep (include/oneshotdet_hip_class_sweep.h); one body for both kernels.
+// class sweep's K for osd_roi_pool_levels_sweep (include/oneshotdet_hip.h); one body for both kernels.
 template <typename T>
 __device__ __forceinline__ void roi_pool_levels_body(const PoolLevels& lv, const float* __restrict__ boxes,
                                                      const int32_t* __restrict__ counts, T* __restrict__ y, int c, int max_rois,
@@ -372,7 +371,7 @@ extern "C" int osd_roi_pool_levels(int n_levels, const void* const* xs, const in
   return osd_check_launch("roi_pool_levels");
 }
 
-// include/oneshotdet_hip_class_sweep.h
+// the class sweep's pooling: sets_per_image ROI sets read one image's maps
 extern "C" int osd_roi_pool_levels_sweep(int n_levels, const void* const* xs, const int32_t* hs, const int32_t* ws,
                                          const float* scales, const float* boxes, const int32_t* counts, void* y, int n_sets,
                                          int sets_per_image, int c, int max_rois, int pool, int sampling_ratio, int y_stride,

@@ -11,7 +11,6 @@
 #include "osd_common.h"
 #include "../../include/oneshotdet_hip_box_modes.h"
 #include "../../include/oneshotdet_hip_soft_labels.h"
-#include "../../include/oneshotdet_hip_neg_support.h"
 
 namespace {
 
@@ -306,7 +305,7 @@ __device__ __forceinline__ float box_focal_grad(float x, int label, float gamma,
 //   OSD_BOX_CLS_L1     L = 1, loss.py:364-365: mean over the [M,M] broadcast of |s_i - t_j|, which has no closed form: the valid rows'
 //                      soft labels go through LDS in tiles of kL1Tile rows and every thread walks every tile for its rows
 //   OSD_BOX_CLS_CXE    L = 2, loss.py:294-296,366-367: -mean([1 - t, t] * log softmax) over the [M,2] tensor, i.e. over 2M elements
-// With FEW_SHOT.NEG_SUPPORT (include/oneshotdet_hip_neg_support.h; NEG, 'ce_loss' only) `pred_neg` holds the same rows scored against the
+// With FEW_SHOT.NEG_SUPPORT (include/oneshotdet_hip.h; NEG, 'ce_loss' only) `pred_neg` holds the same rows scored against the
 // negative support and loss.py:435-444 is added over the K valid rows with label 1: relu(q - p + margin).mean(), p / q = the softmax
 // score of column 1 of pred / pred_neg.  K is counted before the first gradient is written; K == 0 gives 0 (the reference: NaN).
 // The smooth-L1 term, the reduction, the NaN poisoning of labels > 1 and the zeroing of invalid rows are one chain for all modes.

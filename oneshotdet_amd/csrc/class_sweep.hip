@@ -1,4 +1,4 @@
-// Class sweep (include/oneshotdet_hip_class_sweep.h): K category slots per target image in one pass.  The correlation of
+// Class sweep (include/oneshotdet_hip.h): K category slots per target image in one pass.  The correlation of
 // generalized_rcnn.py:307-311, run K times on the same target pyramid, as one launch that reads each map once per GROUP of
 // query vectors instead of once per vector.  HBM-bound: (ceil(K/G) + K) maps of traffic against 2K for the per-pair launches.
 // (The sweep's ROI pooling shares its device code with the per-pair kernel and lives next to it in box_head.hip; the walk of this

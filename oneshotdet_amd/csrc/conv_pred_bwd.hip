@@ -22,7 +22,6 @@
 // LDS image of G and of an X stage: 128-byte rows, 16-byte chunk c of row r at chunk c ^ 2 * ((r >> 1) & 3): the 8 rows x 32 bytes a
 // half-wave takes in a transposed read cover the 64 banks once, and so do the 16 x 16 bytes of a row read's lane group.
 #include "osd_common.h"
-#include "../../include/oneshotdet_hip_pred_bwd.h"
 
 #include <stdlib.h>
 

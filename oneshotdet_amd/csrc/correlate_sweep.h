@@ -6,7 +6,6 @@
 #define OSD_CORRELATE_SWEEP_H
 
 #include "osd_common.h"
-#include "../../include/oneshotdet_hip_class_sweep.h"
 
 namespace {
 

@@ -1,4 +1,4 @@
-// Query gallery (include/oneshotdet_hip_gallery.h): the supports of G gallery slots are enrolled once, and a call detects its images
+// Query gallery (include/oneshotdet_hip.h): the supports of G gallery slots are enrolled once, and a call detects its images
 // against rows of that bank picked by a slot table in device memory.  Two kernels read the enrolled data through the table:
 //   * the class sweep's correlation walk (correlate_sweep.h) with the staged query vectors taken as q[slots[row]]
 //   * the box head's GroupNorm + LeakyReLU (gn_act_rois.h) with the addend map taken as addend[add_index[set] * stride + offset]
@@ -11,7 +11,6 @@
 // the two kernels compiled to before they took the template parameter (their trailing arguments are never read).
 #include "correlate_sweep.h"
 #include "gn_act_rois.h"
-#include "../../include/oneshotdet_hip_gallery.h"
 
 #define OSD_STREAM(s) reinterpret_cast<hipStream_t>(s)
 

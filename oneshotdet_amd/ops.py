@@ -599,7 +599,7 @@ def correlate_levels(xs, qs):
 
 
 def correlate_levels_sweep(xs, qs, classes):
-    """The class sweep's correlation (include/oneshotdet_hip_class_sweep.h): xs = NHWC level maps [n, H_l, W_l, C], qs = [n*classes, C]
+    """The class sweep's correlation (include/oneshotdet_hip.h): xs = NHWC level maps [n, H_l, W_l, C], qs = [n*classes, C]
     fp32 per level -> [n*classes, H_l, W_l, C] per level, row b*classes + k = xs[b] * qs[b*classes + k], in ONE launch that loads
     every map once per group of CLASS_SWEEP_GROUP query vectors.  The bits of correlate_levels on `classes` times replicated xs."""
     _chk_dev(*xs)
@@ -620,7 +620,7 @@ def correlate_levels_sweep(xs, qs, classes):
 
 
 def correlate_levels_gallery(xs, qs, slots, classes):
-    """The query gallery's correlation (include/oneshotdet_hip_gallery.h): xs = NHWC level maps [n, H_l, W_l, C], qs = [G, C] fp32 per
+    """The query gallery's correlation (include/oneshotdet_hip.h): xs = NHWC level maps [n, H_l, W_l, C], qs = [G, C] fp32 per
     level (the enrolled gallery), slots = device int32 [n*classes] of gallery rows -> [n*classes, H_l, W_l, C] per level, row
     b*classes + k = xs[b] * qs[slots[b*classes + k]], in ONE launch.  The bits of correlate_levels_sweep on the gathered vectors
     qs[slots]; nothing is gathered.  The table is validated on the host by its maker (model.check_class_ids): a slot outside
@@ -1402,7 +1402,7 @@ def roi_pool_levels(feats, scales, boxes, counts, pool, sampling_ratio, out=None
 def groupnorm_act_rois(x, gamma, beta, groups=32, eps=1e-5, slope=0.2, addend=None, rois_per_add=1, add_stride=1,
                        add_offset=0, out=None, add_index=None):
     """LeakyReLU(slope)(GroupNorm(groups, C)(x [+ addend map of the ROI's image / shot])) on [R,7,7,C] ROI maps.
-    add_index (the query gallery, include/oneshotdet_hip_gallery.h): device int32, one entry per ROI set of rois_per_add samples; the
+    add_index (the query gallery, include/oneshotdet_hip.h): device int32, one entry per ROI set of rois_per_add samples; the
     addend row of sample i is add_index[i // rois_per_add] * add_stride + add_offset instead of (i // rois_per_add) * add_stride +
     add_offset.  The bits of the plain call on the gathered addend."""
     _chk_dev(x, gamma, beta, addend, add_index)
@@ -1613,7 +1613,7 @@ def proposals_sort_nms(keys, boxes, max_count, levels, topn, thresh, max_keep, c
     return ob, os_, oc
 
 
-# ---------------------------------------------------------------------------------------------------- solver (oneshotdet_hip_solver.h)
+# ---------------------------------------------------------------------------------------------------- solver (osd_solver_set and the `_dev` updates)
 def solver_block(device):
     """The 8-byte solver block { float lr; int32 first_step; } the `_dev` update entries read (8-byte aligned: one int64)."""
     return torch.zeros((1,), device=device, dtype=torch.int64)

@@ -43,7 +43,7 @@ neg_support (FEW_SHOT.NEG_SUPPORT.TURN_ON, generalized_rcnn.py:229-299, box_head
 'ce_loss', one shot, no linear_fusion): every step also gets `neg_queries`, one support crop of another category per image, collated to
 the padded shape of `queries`.  They ride the query backbone as B more rows of the query batch (positives first); the first stage sees the
 first B rows only.  The box head scores the same sampled ROIs against them with the same weights and a margin loss is added
-(train_second_stage.py, include/oneshotdet_hip_neg_support.h).  The state_dict has the keys and shapes of the plain 'ce_loss' model.
+(train_second_stage.py, include/oneshotdet_hip.h).  The state_dict has the keys and shapes of the plain 'ce_loss' model.
 `box_suppress_loss` [2] = (loss_cls_suppress, foreground rows) of the last step.  False (the default): every launch as it is.
 """
 import math
@@ -716,7 +716,7 @@ class TrainEngine(ForwardPass, BackwardPass, SecondStage, Update, State):
         RCCL all-reduce between them launched normally): ~1500 launches per step become two graph launches.  Without a
         schedule the learning rate is baked in at capture time; call capture() again after changing it.  With lr_schedule the
         captured update reads its rate and its first-step flag from an 8-byte device block (osd_sgd_momentum_*_dev,
-        include/oneshotdet_hip_solver.h), which replay_step() rewrites before every replay (osd_solver_set, one small launch
+        include/oneshotdet_hip.h), which replay_step() rewrites before every replay (osd_solver_set, one small launch
         outside the graphs): the replayed steps follow the schedule, and `lr` assigned by hand after the schedule has been taken
         away is honoured too.  The update count (`iteration`) after capture() counts the warm-up steps, which are real training
         steps, and not the captured update, which has not run."""

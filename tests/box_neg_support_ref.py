@@ -12,7 +12,7 @@ With p = softmax(class_logits)[:, 1] and q = softmax(neg_class_logits)[:, 1] of 
     d suppress / d class_logits[r]     = (1 / K) [q_r - p_r + 0.3 > 0] p_r (1 - p_r) * (+1, -1),
     d suppress / d neg_class_logits[r] = (1 / K) [q_r - p_r + 0.3 > 0] q_r (1 - q_r) * (-1, +1),
 since d softmax(x)[1] / d x = s1 (1 - s1) * (-1, +1).  K == 0: the reference's mean of an empty tensor is NaN; the kernel's
-documented answer is 0 with zero gradients (include/oneshotdet_hip_neg_support.h), and `suppress_loss(..., empty="zero")` says so.
+documented answer is 0 with zero gradients (include/oneshotdet_hip.h), and `suppress_loss(..., empty="zero")` says so.
 """
 import torch
 import torch.nn.functional as F

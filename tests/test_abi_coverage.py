@@ -1,23 +1,21 @@
 """CPU: an inventory of include/oneshotdet_hip.h — every declared osd_* function either names a test that calls it (directly or
 through its `ops` wrapper) or is listed, with a reason, as a function that launches nothing.  A new entry point without a row
-fails here; so does a row whose function left the header or whose test no longer exists."""
+fails here; so does a row whose function left the header or whose test no longer exists.  The entries of NAMED are held to more:
+the test's body names the function, and the `ops` wrapper that reaches it is itself called on the GPU."""
 import os
 import re
 
+from abi_utils import declared
+
 TESTS = os.path.dirname(os.path.abspath(__file__))
-
-
-def declared_symbols():
-    """the functions include/oneshotdet_hip.h declares (the regex of tests/test_abi.py)"""
-    src = open(os.path.join(os.path.dirname(TESTS), "include", "oneshotdet_hip.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(osd_[a-z0-9_]+)\s*\(", src)))
 
 
 K, T, S = "test_gpu_kernels.py", "test_gpu_train.py", "test_gpu_support_kernels.py"
 PR, BH, BT = "test_gpu_proposals.py", "test_gpu_box_head.py", "test_gpu_box_train.py"
 EV, TR, G1, FL, QA = "test_gpu_evaluation.py", "test_gpu_transforms.py", "test_gpu_groupnorm_onepass.py", "test_gpu_fcos_loss_modes.py", \
     "test_gpu_query_avgpool.py"
+NS = "test_gpu_box_neg_support.py"
+SO, CS, GA, PB = "test_gpu_solver.py", "test_gpu_class_sweep.py", "test_gpu_gallery.py", "test_gpu_pred_bwd.py"
 _QP = (K, "test_query_pool_levels_equals_the_per_level_launches")
 _PRED = (K, "test_prediction_conv_data_gradient_as_a_gemm_over_the_gathered_dy")
 
@@ -109,12 +107,40 @@ COVERED = {
     "osd_coco_match": (EV, "test_coco_match_flags_equal_the_oracle_per_pair_and_edge_cases"),
     "osd_image_transform": (TR, "test_random_sizes_against_the_oracle"),
     "osd_image_transform_batch": (TR, "test_batched_chain_equals_the_per_image_one_for_mixed_batches"),
+    "osd_box_loss_neg_support": (NS, "test_c_entry_with_padded_strides_null_gradients_bad_labels_and_error_codes"),
+    "osd_solver_set": (SO, "test_solver_set_writes_its_eight_bytes_and_bad_blocks_are_refused"),
+    "osd_sgd_momentum_multi_dev": (SO, "test_dev_entries_match_the_by_value_entries_bit_for_bit"),
+    "osd_sgd_momentum_pack_multi_dev": (SO, "test_dev_entries_match_the_by_value_entries_bit_for_bit"),
+    "osd_correlate_levels_sweep": (CS, "test_sweep_correlation_is_the_per_pair_launch_on_replicated_maps_bit_for_bit"),
+    "osd_roi_pool_levels_sweep": (CS, "test_sweep_roi_pooling_is_the_per_pair_launch_on_replicated_maps_bit_for_bit"),
+    "osd_correlate_levels_gallery": (GA, "test_gallery_correlation_is_the_sweep_launch_on_gathered_vectors_bit_for_bit"),
+    "osd_groupnorm_act_rois_gallery": (GA, "test_gallery_groupnorm_is_the_existing_entry_on_a_gathered_addend_bit_for_bit"),
+    "osd_conv2d_pred_bwd": (PB, "test_unsupported_shapes_return_the_documented_codes"),
+    "osd_pred_bwd_workspace_bytes": (PB, "test_unsupported_shapes_return_the_documented_codes"),
+}
+
+_LOSS = "test_loss_kernel_matches_the_reference_fixture"
+# function -> (what the body of its COVERED test must contain, the `ops` wrapper that reaches it, what the wrapper's body must contain,
+#              the test of the same file that calls the wrapper (None: anywhere in the file), what that test must contain)
+NAMED = {
+    "osd_box_loss_neg_support": ('"osd_box_loss_neg_support"', "box_loss_neg_support", '"osd_box_loss_neg_support"', _LOSS,
+                                 ("ops.box_loss_neg_support(", "grad_stride=")),
+    "osd_solver_set": ('"osd_solver_set"', "solver_set", '"osd_solver_set"', None, ("ops.solver_set(",)),
+    "osd_sgd_momentum_multi_dev": ('"osd_sgd_momentum_multi_dev"', "sgd_momentum_multi_dev", '"osd_sgd_momentum_multi_dev"', None,
+                                   ("ops.sgd_momentum_multi_dev(",)),
+    "osd_sgd_momentum_pack_multi_dev": ('"osd_sgd_momentum_pack_multi_dev"', "sgd_momentum_pack_multi_dev",
+                                        '"osd_sgd_momentum_pack_multi_dev"', None, ("ops.sgd_momentum_pack_multi_dev(",)),
+    # called through the bound library (lib.<name>(...)), not by name through _lib.call
+    "osd_conv2d_pred_bwd": ("osd_conv2d_pred_bwd", "pred_bwd_fused", '"osd_conv2d_pred_bwd"', None, ("o.pred_bwd_fused(",)),
+    "osd_pred_bwd_workspace_bytes": ("osd_pred_bwd_workspace_bytes", "pred_bwd_fused", "osd_pred_bwd_workspace_bytes(", None,
+                                     ("o.pred_bwd_fused(",)),
 }
 
 # functions that launch no kernel of their own to compare with a reference
 NO_LAUNCH = {
     "osd_last_error_string": "returns the calling thread's last error message",
     "osd_abi_version": "returns a constant (checked on the CPU by test_abi.py)",
+    "osd_class_sweep_group": "returns a constant (checked against its #define on the CPU by test_abi.py)",
     "osd_query_avgpool_workspace_bytes": "host-side size query",
     "osd_nms_workspace_bytes": "host-side size query (value pinned by test_abi.py)",
     "osd_nms_single_workspace_bytes": "host-side size query",
@@ -128,14 +154,35 @@ NO_LAUNCH = {
 
 
 def test_every_exported_function_names_a_test_or_a_reason():
-    declared = set(declared_symbols())
+    names = set(declared())
     listed = set(COVERED) | set(NO_LAUNCH)
     assert not (set(COVERED) & set(NO_LAUNCH))
-    assert declared - listed == set(), "entry points without a test: add one and a row to COVERED"
-    assert listed - declared == set(), "rows for functions the header no longer declares"
+    assert names - listed == set(), "entry points without a test: add one and a row to COVERED"
+    assert listed - names == set(), "rows for functions the header no longer declares"
     assert all(reason.strip() for reason in NO_LAUNCH.values())
     sources = {}
     for name, (fname, test) in sorted(COVERED.items()):
         if fname not in sources:
             sources[fname] = open(os.path.join(TESTS, fname)).read()
         assert re.search(r"^def %s\(" % re.escape(test), sources[fname], flags=re.M), "%s: %s has no %s" % (name, fname, test)
+
+
+def body(src, test):
+    m = re.search(r"^def %s\(.*?(?=^def |^@pytest|\Z)" % re.escape(test), src, flags=re.S | re.M)
+    assert m, test
+    return m.group(0)
+
+
+def test_named_entries_are_called_by_their_test_and_through_their_ops_wrapper():
+    assert set(NAMED) <= set(COVERED)
+    ops_src = open(os.path.join(os.path.dirname(TESTS), "oneshotdet_amd", "ops.py")).read()
+    for fn, (needle, wrapper, wrapper_needle, through, also) in NAMED.items():
+        fname, test = COVERED[fn]
+        src = open(os.path.join(TESTS, fname)).read()
+        assert "pytestmark = pytest.mark.gpu" in src, fname
+        assert needle in body(src, test), (fn, test)
+        wbody = re.search(r"^def %s\(.*?(?=^def |\Z)" % wrapper, ops_src, flags=re.S | re.M).group(0)
+        assert wrapper_needle in wbody, (fn, wrapper)
+        where = body(src, through) if through else src
+        for word in also:
+            assert word in where, (fn, through, word)

@@ -57,7 +57,7 @@ def test_header_and_third_binding_table_agree():
         assert len(params.split(",")) == len(args), name
     # the build depends on the header, and the ABI version is not part of this change
     from oneshotdet_amd import build
-    assert HEADER in open(build.__file__).read()
+    assert HEADER in [os.path.basename(h) for h in build.HEADERS]
     assert _lib.ABI_VERSION == 4
 
 

@@ -278,7 +278,7 @@ def test_checkpoint_round_trip_and_resume_refusal(tmp_path):
 def test_documents_describe_the_option():
     for doc in ("README.md", "DESIGN.md", "INTEGRATION.md"):
         text = open(os.path.join(ROOT, doc)).read()
-        assert "neg_support" in text and "oneshotdet_hip_neg_support.h" in text, doc
+        assert "neg_support" in text and "oneshotdet_hip.h" in text, doc
     design = open(os.path.join(ROOT, "DESIGN.md")).read()
     assert "osd_box_loss_neg_support" in design and "K == 0" in design and "profiles/neg_support_step.md" in design
     assert "stacked" in design

@@ -1,4 +1,4 @@
-"""GPU: the prediction convs' fused backward launch (osd_conv2d_pred_bwd, include/oneshotdet_hip_pred_bwd.h; ops.pred_bwd_fused):
+"""GPU: the prediction convs' fused backward launch (osd_conv2d_pred_bwd, include/oneshotdet_hip.h; ops.pred_bwd_fused):
 data gradient + weight / bias gradient of a 3x3 conv with 2 or 4 outputs over all FPN levels in one launch that keeps the gathered
 dy matrix G in LDS.  Bars: tests/conv_ref.py (one bf16 rounding of the float64 result for dX, ACC_TOL for the accumulated dW / db)."""
 import ctypes as C

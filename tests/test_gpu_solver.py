@@ -1,4 +1,4 @@
-"""GPU: include/oneshotdet_hip_solver.h — the optimiser update with its learning rate in device memory — and the learning-rate
+"""GPU: osd_solver_set and the `_dev` update entries — the optimiser update with its learning rate in device memory — and the learning-rate
 schedule through the training engine (TrainEngine(lr_schedule=), capture / replay_step, checkpoints).
 
 Kernel tests: the small entry tables of tests/test_gpu_support_kernels.py (SGD_ENTRIES: every path of the update kernels — offsets
