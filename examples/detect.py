@@ -57,7 +57,16 @@ def main():
     ap.add_argument("--gallery", type=int, default=0,
                     help="G: enroll G synthetic supports once (OneShotDetector.enroll) and detect three batches of images against the "
                          "bank, each asking for its own labels")
+    ap.add_argument("--supp-aug", type=int, default=1, metavar="N",
+                    help="the model was trained with query augmentation groups (FEW_SHOT.SUPP_AUG, NUM_SUPP_AUG = N - 1): every support "
+                         "is passed as N consecutive rows, here the support and its horizontal flip in turn")
+    ap.add_argument("--supp-aug-method", default="avg", choices=list(spec.SUPP_AUG_METHODS), help="FEW_SHOT.SUPP_AUG_METHOD")
     args = ap.parse_args()
+    supp_aug, supp_aug_method = spec.supp_aug_mode(args.supp_aug, args.supp_aug_method, args.neg_support and not args.first_stage_only)
+
+    def groups(supports):
+        """every support -> its group of supp_aug consecutive rows: the support, its horizontal flip, the support, ..."""
+        return [s if a % 2 == 0 else s.flip(-1) for s in supports for a in range(supp_aug)]
     siamese = not args.shared_backbone
     roialign = not args.no_supp_roialign
     if args.checkpoint:
@@ -86,19 +95,20 @@ def main():
         print("synthetic weights (no checkpoint given)")
     if args.first_stage_only:
         options.update(linear_fusion=False, neg_support=False)
-    det = modules.OneShotDetector(sd, dtype=torch.bfloat16 if args.dtype == "bf16" else torch.float32, **options)
+    det = modules.OneShotDetector(sd, dtype=torch.bfloat16 if args.dtype == "bf16" else torch.float32,
+                                 supp_aug=supp_aug, supp_aug_method=supp_aug_method, **options)
     # two targets and two queries of different sizes
     targets = [torch.from_numpy(synth.make_images("ex.t%d" % i, 1, h, w)[0]) for i, (h, w) in enumerate([(480, 640), (512, 384)])]
     queries = [torch.from_numpy(synth.make_images("ex.q%d" % i, 1, h, w)[0]) for i, (h, w) in enumerate([(127, 127), (96, 160)])]
     images = layers.to_image_list(targets, size_divisible=spec.SIZE_DIVISIBILITY)
-    images_supp = layers.to_image_list(queries, size_divisible=spec.SIZE_DIVISIBILITY)
+    images_supp = layers.to_image_list(groups(queries), size_divisible=spec.SIZE_DIVISIBILITY)
     print("padded batch", tuple(images.tensors.shape), "true sizes", images.image_sizes)
     if args.gallery > 0:
         G = args.gallery
         sizes = [(127, 127), (96, 160)]
         supports = [torch.from_numpy(synth.make_images("ex.g%d" % g, 1, *sizes[g % 2])[0]) for g in range(G)]
         labels = [1 + (7 * g) % 80 for g in range(G)]
-        bank = det.enroll(layers.to_image_list(supports, size_divisible=spec.SIZE_DIVISIBILITY), labels)       # the query branch, once
+        bank = det.enroll(layers.to_image_list(groups(supports), size_divisible=spec.SIZE_DIVISIBILITY), labels)       # the query branch, once
         print("enrolled %d gallery slots, labels %s" % (bank.slots, labels))
         K = min(3, G)
         for step in range(3):                                    # a stream of image batches against the same bank
@@ -118,7 +128,7 @@ def main():
         K = args.classes
         sizes = [(127, 127), (96, 160)]
         supports = [torch.from_numpy(synth.make_images("ex.q%d.%d" % (b, k), 1, *sizes[(b + k) % 2])[0]) for b in range(2) for k in range(K)]
-        images_supp = layers.to_image_list(supports, size_divisible=spec.SIZE_DIVISIBILITY)
+        images_supp = layers.to_image_list(groups(supports), size_divisible=spec.SIZE_DIVISIBILITY)
         ids = [[1 + (17 * b + k) % 80 for k in range(K)] for b in range(2)]
         results = det(images, images_supp, target_ids=ids)
         torch.cuda.synchronize()

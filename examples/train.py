@@ -84,6 +84,11 @@ def main():
                          "loss_cls_suppress (FEW_SHOT.NEG_SUPPORT; 'ce_loss', one shot, no --linear-fusion).  The reference ships no "
                          "rule for choosing the negative support (its dataset's negative category is always -1); this example's own "
                          "rule: sample i's negative support is the support crop of sample (i + 1) mod batch")
+    ap.add_argument("--supp-aug", type=int, default=1, metavar="N",
+                    help="query augmentation groups (FEW_SHOT.SUPP_AUG, NUM_SUPP_AUG = N - 1): every support is N consecutive rows merged "
+                         "behind the query backbone.  Here 1 (off) or 2 (the crop and its horizontal flip, the dataset's supp_aug=True); "
+                         "the dataset has no colour jitter for more")
+    ap.add_argument("--supp-aug-method", default="avg", choices=list(spec.SUPP_AUG_METHODS), help="FEW_SHOT.SUPP_AUG_METHOD")
     rec = solver.LRSchedule.of_record()
     ap.add_argument("--lr-steps", default=",".join(str(m) for m in rec.milestones), help="iterations at which the rate is multiplied by "
                     "--lr-gamma, comma separated (SOLVER.STEPS); '' = none")
@@ -103,6 +108,10 @@ def main():
                    linear_fusion=args.linear_fusion and not args.first_stage_only, neg_support=args.neg_support)
     # refused here, by name: l1_loss / cxe_loss without --soft-labeling, --neg-support in a combination it does not exist in
     spec.check_options("the example", not args.first_stage_only, **options)
+    supp_aug, supp_aug_method = spec.supp_aug_mode(args.supp_aug, args.supp_aug_method, args.neg_support)
+    if supp_aug not in (1, 2):
+        raise SystemExit("--supp-aug %d: the dataset yields a support crop and its horizontal flip (supp_aug=True), which is --supp-aug 2; "
+                         "it has no colour-jitter supports for a larger group" % supp_aug)
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
     dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float32
@@ -110,7 +119,8 @@ def main():
         **{name: options[name] for name in spec.SHAPE_OPTIONS})
 
     def make_engine(sd):
-        return train.TrainEngine(sd, dtype=dtype, lr=rec.base_lr, second_stage=not args.first_stage_only, lr_schedule=schedule, **options)
+        return train.TrainEngine(sd, dtype=dtype, lr=rec.base_lr, second_stage=not args.first_stage_only, lr_schedule=schedule,
+                                 supp_aug=supp_aug, supp_aug_method=supp_aug_method, **options)
     start = 0
     last = os.path.join(args.out, "last_checkpoint")
     if args.resume and os.path.exists(last):
@@ -131,20 +141,24 @@ def main():
         eng.attach_exchange(dist.group.WORLD)
     tf_img, tf_supp = T.build_transforms(min_size=480, max_size=800, supp_min_size=128, supp_max_size=192, is_train=True)
     coco, pix = synthetic_coco(np.random.RandomState(1234))                # the same annotation set on every rank
-    ds = dataset.FewShotCocoDataset(coco, lambda info: pix[info["id"]], is_train=True, shot=1, supp_area_threshold=40 * 40)
+    ds = dataset.FewShotCocoDataset(coco, lambda info: pix[info["id"]], is_train=True, shot=1, supp_area_threshold=40 * 40,
+                                    supp_aug=supp_aug == 2)
     os.makedirs(args.out, exist_ok=True)
     for it in range(start, args.iters):
         imgs, supps, targets = [], [], []
         for b in range(args.batch):
             item = ds[((it * world + rank) * args.batch + b) % len(ds)]       # DistributedSampler's split: every rank its own items
             dimg, tgt = T.DeviceImage(item["img"]), item["target"]
-            supp = T.DeviceImage(item["img_supp"][0])                          # the support crop (coco.py:341)
             # the Compose's Resize and flip steps (Normalize is fused into the collation below)
             for t in tf_img.transforms[:2]:
                 dimg, tgt = t(dimg, tgt)
-            for t in tf_supp.transforms[:2]:
-                supp, _ = t(supp, None)
-            imgs.append(dimg); supps.append(supp); targets.append(tgt)
+            imgs.append(dimg); targets.append(tgt)
+            # the support crop (coco.py:341); with --supp-aug 2 followed by its flip (coco.py:343-349): one group of consecutive rows
+            for crop in item["img_supp"][:supp_aug]:
+                supp = T.DeviceImage(crop)
+                for t in tf_supp.transforms[:2]:
+                    supp, _ = t(supp, None)
+                supps.append(supp)
         images = T.collate(imgs, spec.SIZE_DIVISIBILITY, stem_dtype=dtype)
         queries = T.collate(supps, spec.SIZE_DIVISIBILITY, stem_dtype=dtype)
         # the same crops rotated by one: the same padded shape as `queries`, which the engine requires

@@ -170,6 +170,13 @@ SIGNATURES_SOFT_LABELS = {
     "osd_box_loss_soft": (_i, [_p, _p, _p, _p, _i, _i, _i, _f, _f, _p, _p, _i, _i, _p, _i, _p]),
 }
 
+# include/oneshotdet_hip_supp_aug.h: query augmentation groups (FEW_SHOT.SUPP_AUG, SUPP_AUG_METHOD 'avg' / 'max')
+SUPP_AUG_AVG, SUPP_AUG_MAX = 0, 1
+SIGNATURES_SUPP_AUG = {
+    "osd_supp_aug_reduce_levels": (_i, [_i, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
+    "osd_supp_aug_reduce_levels_bwd": (_i, [_i, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
+}
+
 PRED_BWD_BOTH, PRED_BWD_DGRAD, PRED_BWD_WGRAD = 0, 1, 2       # `flags` of osd_conv2d_pred_bwd (OSD_PRED_BWD_*)
 
 _lib = None
@@ -190,7 +197,8 @@ def load():
                        "__graft_entry__.build(); there is no CPU/eager fallback" % LIB_PATH)
     import torch  # noqa: F401  (loads libamdhip64 first)
     lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_BOX_MODES.items()) + list(SIGNATURES_SOFT_LABELS.items()):
+    for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_BOX_MODES.items()) + list(SIGNATURES_SOFT_LABELS.items()) + \
+            list(SIGNATURES_SUPP_AUG.items()):
         fn = getattr(lib, name)   # AttributeError if the symbol is missing
         fn.restype = res
         fn.argtypes = args

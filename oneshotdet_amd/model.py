@@ -240,6 +240,13 @@ def run_query_pool(qfeats, q_sizes, batch, supp_roialign=True):
     return pooled
 
 
+def run_supp_aug(qfeats, aug, method):
+    """FEW_SHOT.SUPP_AUG (generalized_rcnn.py:280-288): every group of `aug` consecutive maps of the query pyramid merged into one
+    ('avg' / 'max'), all levels in one launch, directly behind the query backbone: the query pooling, the second stage's query ROI
+    pooling and enroll see one map per group.  aug = 1: the maps as they are, nothing launched."""
+    return qfeats if aug == 1 else ops.supp_aug_reduce_levels(qfeats, aug, method)
+
+
 def run_correlate(feats, pooled, classes=1, bank=None, slots=None):
     """generalized_rcnn.py:307-311: all five levels in one launch.  classes = K (the class sweep): pooled has K rows per image of
     feats and the result K maps per image, row b*K + k (ops.correlate_levels_sweep: each map loaded once per group of vectors).
@@ -490,10 +497,17 @@ class HotPathEngine(object):
     trained with the other setting is refused (ValueError naming the option).
     neg_support (FEW_SHOT.NEG_SUPPORT.TURN_ON): how the model was trained; validated against the combinations the option exists in
     ('ce_loss', no linear_fusion) and changes nothing computed: the reference computes the negative logits in evaluation and discards
-    them (box_head.py:156-161,175-177), and the state_dict has the plain 'ce_loss' model's keys and shapes."""
+    them (box_head.py:156-161,175-177), and the state_dict has the plain 'ce_loss' model's keys and shapes.
+    supp_aug / supp_aug_method (FEW_SHOT.SUPP_AUG with NUM_SUPP_AUG = supp_aug - 1, SUPP_AUG_METHOD 'avg' / 'max'): every query is a group
+    of supp_aug consecutive rows (a support crop and its augmentations); the query backbone runs on all of them and run_supp_aug merges
+    each group into one map per level before anything else reads the query pyramid.  `queries` then holds B*K*S*supp_aug rows (enroll:
+    G*shots*supp_aug) and a group's members must have one size.  Ordinary keywords like `shots`: the merge has no weights, and 1 (the
+    default) launches nothing."""
 
     def __init__(self, state_dict, dtype=torch.float32, device="cuda", siamese_backbone=True, supp_roialign=True,
-                 box_cls_loss="ce_loss", soft_labeling=False, soft_labeling_func="linear", linear_fusion=False, neg_support=False):
+                 box_cls_loss="ce_loss", soft_labeling=False, soft_labeling_func="linear", linear_fusion=False, neg_support=False,
+                 supp_aug=1, supp_aug_method="avg"):
+        self.supp_aug, self.supp_aug_method = spec.supp_aug_mode(supp_aug, supp_aug_method, neg_support)
         # spec.MODEL_OPTIONS: ValueError by name before anything is built; the rows this engine takes become attributes
         given = spec.options_in(locals())
         options = spec.check_options("the HotPathEngine", True, **given)
@@ -535,7 +549,8 @@ class HotPathEngine(object):
 
     def enroll(self, queries, shots=1, labels=None):
         """The query branch, once: queries [G*S,3,h,w] (or an ImageList / ops.PackedImages of G*S supports), row g*S + s = shot s of
-        gallery slot g -> QueryBank.  Runs what detect runs per call on its queries (the query backbone + FPN, the query pooling, and
+        gallery slot g -> QueryBank.  With supp_aug = A > 1: G*S*A rows, row (g*S + s)*A + a = member a of that shot's group.  Runs what
+        detect runs per call on its queries (the query backbone + FPN, the query pooling, and
         with a packed second stage supproi_pooling and the query half of the box head's first conv), keeps the results, and
         detect(images, bank=bank, class_ids=...) then launches none of them.  labels: one (hashable) label per slot, for
         OneShotDetector's target_ids."""
@@ -546,7 +561,9 @@ class HotPathEngine(object):
         if isinstance(queries, ImageList):
             queries, query_sizes = queries.tensors, queries.image_sizes
         shots = int(shots)
-        rows = queries.shape[0]
+        aug = self.supp_aug
+        q_sizes = spec.group_query_sizes([tuple(queries.shape[-2:])] * queries.shape[0] if query_sizes is None else query_sizes, aug)
+        rows = queries.shape[0] // aug
         if shots < 1 or rows == 0 or rows % shots != 0:
             raise ValueError("%d support rows are no multiple of shots = %d (queries holds G*S rows: S shots of each of G gallery slots)"
                              % (rows, shots))
@@ -556,8 +573,7 @@ class HotPathEngine(object):
             if len(labels) != g or len(set(labels)) != g:
                 raise ValueError("labels: one distinct label per gallery slot, %d slots (got %d labels, %d distinct)"
                                  % (g, len(labels), len(set(labels))))
-        q_sizes = [tuple(queries.shape[-2:])] * rows if query_sizes is None else list(query_sizes)
-        qfeats = run_backbone(self.supp_backbone, queries, self.dtype)
+        qfeats = run_supp_aug(run_backbone(self.supp_backbone, queries, self.dtype), aug, self.supp_aug_method)
         pooled = run_query_pool(qfeats, q_sizes, g, self.supp_roialign)
         q_half = query_roi = None
         if self.box_head is not None:
@@ -588,32 +604,42 @@ class HotPathEngine(object):
         classes = K (the class sweep): queries holds B*K*S rows; the target backbone runs on the B images once, the query branch pools
         B*K category slots of S shots, and `combined` has B*K rows (b*K + k) from one sweep launch over the B-row features.
         bank (+ class_ids, see detect) instead of queries: only the target backbone runs; `combined` is one gallery launch over the
-        bank's pooled vectors, and the query features returned are None."""
+        bank's pooled vectors, and the query features returned are None.
+        supp_aug = A > 1: queries holds B*K*S*A rows; the query features returned are the merged ones (B*K*S rows), the backbone's own
+        are kept in self.unmerged_query_features."""
+        self.unmerged_query_features = None
         if bank is not None or queries is None:
             table = self._bank_table(images.shape[0], queries, bank, class_ids, classes)
             feats = run_backbone(self.backbone, images, self.dtype)
             return feats, None, bank.pooled, run_correlate(feats, None, table.classes, bank=bank, slots=table.dev)
         if class_ids is not None:
             raise ValueError("class_ids picks slots of a QueryBank: give bank= instead of queries")
+        aug, method = self.supp_aug, self.supp_aug_method
+        # one size per group, refused (nothing launched yet) where a group's members differ
+        q_sizes = spec.group_query_sizes([tuple(queries.shape[-2:])] * queries.shape[0] if query_sizes is None else query_sizes, aug)
         if classes != 1:
-            check_classes(images.shape[0], queries.shape[0], classes)
+            check_classes(images.shape[0], len(q_sizes), classes)
         batch = images.shape[0] * classes
-        q_sizes = [tuple(queries.shape[-2:])] * queries.shape[0] if query_sizes is None else list(query_sizes)
         if concurrent and LOCKSTEP:
-            feats, qfeats = run_backbones(self.backbone, self.supp_backbone, images, queries, self.dtype)
+            feats, raw = run_backbones(self.backbone, self.supp_backbone, images, queries, self.dtype)
+            qfeats = run_supp_aug(raw, aug, method)
             pooled = run_query_pool(qfeats, q_sizes, batch, self.supp_roialign)
         elif concurrent:
             main, side = _streams.current(), self.side_streams()[0]
             side.wait_stream(main)
             with _streams.on(side):
-                qfeats = run_backbone(self.supp_backbone, queries, self.dtype)
+                raw = run_backbone(self.supp_backbone, queries, self.dtype)
+                qfeats = run_supp_aug(raw, aug, method)
                 pooled = run_query_pool(qfeats, q_sizes, batch, self.supp_roialign)
             feats = run_backbone(self.backbone, images, self.dtype)
             main.wait_stream(side)
         else:
             feats = run_backbone(self.backbone, images, self.dtype)
-            qfeats = run_backbone(self.supp_backbone, queries, self.dtype)
+            raw = run_backbone(self.supp_backbone, queries, self.dtype)
+            qfeats = run_supp_aug(raw, aug, method)
             pooled = run_query_pool(qfeats, q_sizes, batch, self.supp_roialign)
+        if aug != 1:
+            self.unmerged_query_features = raw
         combined = run_correlate(feats, pooled, classes)
         return feats, qfeats, pooled, combined
 
@@ -639,6 +665,8 @@ class HotPathEngine(object):
         feats, qfeats, pooled, combined = self.forward_features(images, queries, concurrent, query_sizes, classes, None, class_ids)
         head = run_head(self.head, combined, self.side_streams() if concurrent else None)
         out = dict(features=feats, query_features=qfeats, pooled=pooled, combined=combined, head=head)
+        if self.supp_aug != 1:         # query_features are the merged maps; the query backbone's own, supp_aug rows per group
+            out["query_features_unmerged"] = self.unmerged_query_features
         if classes != 1:
             out["classes"] = classes
         return out
@@ -682,11 +710,14 @@ class HotPathEngine(object):
             query_sizes = queries.image_sizes
         if isinstance(queries, ImageList):
             queries, query_sizes = queries.tensors, queries.image_sizes
+        aug = self.supp_aug
+        if aug != 1:                            # one size per group for everything behind the merge; unequal members refused here
+            grouped = spec.group_query_sizes([tuple(queries.shape[-2:])] * queries.shape[0] if query_sizes is None else query_sizes, aug)
         if classes != 1:                        # the class sweep: the rest of this call runs on B*K rows, each image's true size K times
-            check_classes(images.shape[0], queries.shape[0], classes)
+            check_classes(images.shape[0], queries.shape[0] // aug, classes)
             if image_sizes is not None:
                 image_sizes = [tuple(s) for s in image_sizes for _ in range(classes)]
-        shots = queries.shape[0] // (images.shape[0] * classes)
+        shots = queries.shape[0] // (images.shape[0] * classes * aug)
         if second_stage:                        # refused before anything is launched
             from .box_head import check_shots
             check_shots(self.box_cls_loss, shots)
@@ -697,6 +728,8 @@ class HotPathEngine(object):
         out["proposals"] = run_proposals(out["head"], h, w, pre, post, spec.NMS_THRESH, cuda_nms, image_sizes=image_sizes)
         if second_stage:
             q_sizes = query_sizes if query_sizes is not None else tuple(queries.shape[-2:])
+            if aug != 1 and query_sizes is not None:
+                q_sizes = grouped
             out["detections"] = self.box_detect(out["features"], out["query_features"], q_sizes,
                                                 out["proposals"][0], out["proposals"][2], h, w, shots=shots, cuda_nms=cuda_nms,
                                                 image_sizes=image_sizes, classes=classes)

@@ -214,20 +214,25 @@ class OneShotDetector(nn.Module):
     the supports were enrolled once); nested target_ids[i] are then labels of the bank (None: all of them, in the bank's order), and
     the result is again one merged BoxList per image.  The options (spec.MODEL_OPTIONS) are model.HotPathEngine's and go to
     it as they are: which model the state_dict is of (siamese_backbone=False: no `supp_backbone`, the query goes through
-    `backbone`) and how it was trained."""
+    `backbone`) and how it was trained.  supp_aug / supp_aug_method (FEW_SHOT.SUPP_AUG, HotPathEngine): images_supp (and enroll's)
+    carries supp_aug consecutive rows per support, B*S*supp_aug in all, and shots = rows // (B * supp_aug)."""
 
     def __init__(self, state_dict, dtype=torch.float32, device="cuda", siamese_backbone=True, supp_roialign=True,
-                 box_cls_loss="ce_loss", soft_labeling=False, soft_labeling_func="linear", linear_fusion=False, neg_support=False):
+                 box_cls_loss="ce_loss", soft_labeling=False, soft_labeling_func="linear", linear_fusion=False, neg_support=False,
+                 supp_aug=1, supp_aug_method="avg"):
+        supp_aug, supp_aug_method = spec.supp_aug_mode(supp_aug, supp_aug_method, neg_support)
         options = spec.options_in(locals())
         super(OneShotDetector, self).__init__()
-        self.engine = model.HotPathEngine(state_dict, dtype=dtype, device=device, **options)
+        self.engine = model.HotPathEngine(state_dict, dtype=dtype, device=device, supp_aug=supp_aug, supp_aug_method=supp_aug_method,
+                                          **options)
         self.second_stage = self.engine.box_head is not None
 
     def state_dict(self, *a, **k):
         return dict(self.engine.sd)
 
     def enroll(self, images_supp, labels, shots=1):
-        """The supports of a gallery, once: images_supp = G*shots images (row g*shots + s), labels = one distinct label per slot
+        """The supports of a gallery, once: images_supp = G*shots images (row g*shots + s; G*shots*supp_aug with supp_aug, the
+        members of a support's group in consecutive rows), labels = one distinct label per slot
         -> model.QueryBank to pass as `images_supp` of forward (HotPathEngine.enroll)."""
         images_supp = layers.to_image_list(images_supp)
         qs = layers.ImageList(images_supp.tensors.to(self.engine.device, torch.float32), images_supp.image_sizes)

@@ -571,6 +571,65 @@ def query_avgpool_levels_bwd(dqs, shapes, shots, dtype):
     return outs
 
 
+SUPP_AUG_METHODS = {"avg": _lib.SUPP_AUG_AVG, "max": _lib.SUPP_AUG_MAX}      # OSD_SUPP_AUG_* of include/oneshotdet_hip_supp_aug.h
+
+
+def _supp_aug_method(method):
+    if method not in SUPP_AUG_METHODS:
+        raise ValueError("supp_aug_method must be one of %s (FEW_SHOT.SUPP_AUG_METHOD), not %r" % (", ".join(SUPP_AUG_METHODS), method))
+    return SUPP_AUG_METHODS[method]
+
+
+def _level_views(shapes, device, dtype):
+    """one buffer, one contiguous view per level (every level's size is a multiple of its 16-byte channel groups)"""
+    sizes = [int(sh[0] * sh[1] * sh[2] * sh[3]) for sh in shapes]
+    flat = torch.empty((sum(sizes),), device=device, dtype=dtype)
+    outs, off = [], 0
+    for sh, n in zip(shapes, sizes):
+        outs.append(flat[off:off + n].view(tuple(sh)))
+        off += n
+    return outs
+
+
+def supp_aug_reduce_levels(xs, aug, method):
+    """FEW_SHOT.SUPP_AUG (generalized_rcnn.py:280-288): xs[l] NHWC [G * aug, h, w, C], group g = rows g*aug .. g*aug + aug - 1
+    (feat.split(aug, dim=0)) -> [G, h, w, C] per level in the same dtype (views of one buffer), ALL levels in one launch.  method
+    'avg': the members added in member order in fp32, divided by aug, rounded once; 'max': the exact maximum."""
+    code = _supp_aug_method(method)
+    _chk_dev(*xs)
+    k, aug = len(xs), int(aug)
+    r, c = xs[0].shape[0], xs[0].shape[-1]
+    if aug < 1 or r % aug != 0 or not all(x.shape[0] == r and x.shape[-1] == c and x.dtype == xs[0].dtype for x in xs):
+        raise ValueError("supp_aug_reduce_levels: %d rows are no multiple of aug = %d, or the levels differ in rows, channels or dtype"
+                         % (r, aug))
+    xs = [x.contiguous() for x in xs]
+    ys = _level_views([(r // aug, x.shape[1], x.shape[2], c) for x in xs], xs[0].device, xs[0].dtype)
+    _lib.call("osd_supp_aug_reduce_levels", k, _ptr_array(xs), _ptr_array(ys), (C.c_int32 * k)(*[x.shape[1] * x.shape[2] for x in xs]),
+              r // aug, aug, c, _dt(xs[0]), code, _stream())
+    _rec("supp_aug_reduce", xs=xs, aug=aug, method=method, outs=ys)
+    return ys
+
+
+def supp_aug_reduce_levels_bwd(xs, dys, aug, method):
+    """Backward of supp_aug_reduce_levels: xs[l] the forward's input [G * aug, h, w, C], dys[l] [G, h, w, C] in the same dtype -> the
+    gradient of xs (views of one buffer, every element written) in one launch.  'avg': dy / aug to every member; 'max': the whole dy
+    to the lowest-index member that attains the maximum of xs, 0 to the others (torch.max(dim=1)'s CPU backward)."""
+    code = _supp_aug_method(method)
+    _chk_dev(*(list(xs) + list(dys)))
+    k, aug = len(xs), int(aug)
+    r, c = xs[0].shape[0], xs[0].shape[-1]
+    if aug < 1 or r % aug != 0 or len(dys) != k or not all(
+            x.shape[0] == r and x.dtype == xs[0].dtype and d.dtype == x.dtype and
+            tuple(d.shape) == (r // aug,) + tuple(x.shape[1:]) for x, d in zip(xs, dys)):
+        raise ValueError("supp_aug_reduce_levels_bwd: dys must hold one [%d // %d, h, w, C] map per level in the dtype of xs" % (r, aug))
+    xs, dys = [x.contiguous() for x in xs], [d.contiguous() for d in dys]
+    dxs = _level_views([tuple(x.shape) for x in xs], xs[0].device, xs[0].dtype)
+    _lib.call("osd_supp_aug_reduce_levels_bwd", k, _ptr_array(xs), _ptr_array(dys), _ptr_array(dxs),
+              (C.c_int32 * k)(*[x.shape[1] * x.shape[2] for x in xs]), r // aug, aug, c, _dt(xs[0]), code, _stream())
+    _rec("supp_aug_reduce_bwd", xs=xs, dys=dys, aug=aug, method=method, outs=dxs)
+    return dxs
+
+
 def correlate(x, q, out=None):
     """x NHWC [N,H,W,C] * q [N,C] fp32 (broadcast over H, W)."""
     _chk_dev(x, q)

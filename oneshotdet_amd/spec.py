@@ -154,6 +154,49 @@ def check_neg_support(neg_support=False, second_stage=True, linear_fusion=False,
     return True
 
 
+SUPP_AUG_METHODS = ("avg", "max")      # FEW_SHOT.SUPP_AUG_METHOD as supported; index = OSD_SUPP_AUG_* of include/oneshotdet_hip_supp_aug.h
+SUPP_AUG_MAX_GROUP = 8                 # members of a group the merge kernel takes
+
+
+def supp_aug_mode(supp_aug=1, supp_aug_method="avg", neg_support=False):
+    """-> (int A, str method) of FEW_SHOT.SUPP_AUG / NUM_SUPP_AUG / SUPP_AUG_METHOD: A = NUM_SUPP_AUG + 1 consecutive query rows (a
+    support crop and its augmentations) are merged into one map per FPN level in front of every pooling (generalized_rcnn.py:235-294);
+    A = 1 is FEW_SHOT.SUPP_AUG False.  Like `shots` this is a keyword of the engines and not a row of MODEL_OPTIONS: the merge has no
+    weights, and a checkpoint does not record it.  ValueError, by config name, for a group size outside 1 .. 8, a method the
+    reference does not have, 'conv' (it adds a `supp_aug_conv.0.weight` parameter: not supported), and A > 1 with a negative support
+    (the reference merges only the positive support for 'avg' / 'max', :285-288: that model does not exist)."""
+    if isinstance(supp_aug, bool) or int(supp_aug) != supp_aug or not 1 <= int(supp_aug) <= SUPP_AUG_MAX_GROUP:
+        raise ValueError("supp_aug must be an integer in 1 .. %d (FEW_SHOT.NUM_SUPP_AUG + 1 rows per query group; 1 = FEW_SHOT.SUPP_AUG "
+                         "False), not %r" % (SUPP_AUG_MAX_GROUP, supp_aug))
+    if supp_aug_method == "conv":
+        raise ValueError("supp_aug_method 'conv' (FEW_SHOT.SUPP_AUG_METHOD) is not supported: it adds a supp_aug_conv.0.weight "
+                         "parameter to the model (generalized_rcnn.py:75-80); only %s" % " and ".join(repr(m) for m in SUPP_AUG_METHODS))
+    if supp_aug_method not in SUPP_AUG_METHODS:
+        raise ValueError("supp_aug_method must be one of %s (FEW_SHOT.SUPP_AUG_METHOD), not %r" % (", ".join(SUPP_AUG_METHODS), supp_aug_method))
+    if int(supp_aug) > 1 and neg_support:
+        raise ValueError("supp_aug=%d (FEW_SHOT.SUPP_AUG) does not exist with neg_support=True (FEW_SHOT.NEG_SUPPORT): the reference "
+                         "merges only the positive support's group (generalized_rcnn.py:285-288); pass supp_aug=1 or neg_support=False"
+                         % int(supp_aug))
+    return int(supp_aug), str(supp_aug_method)
+
+
+def group_query_sizes(q_sizes, aug):
+    """The members of a query group must have equal sizes (the reference asserts it, generalized_rcnn.py:236-250): one (h, w) per
+    group of `aug` consecutive rows; ValueError naming the first group whose members differ."""
+    if aug == 1:
+        return [tuple(s) for s in q_sizes]
+    q_sizes = [tuple(int(v) for v in s) for s in q_sizes]
+    if len(q_sizes) % aug != 0:
+        raise ValueError("%d query rows are no multiple of supp_aug = %d (FEW_SHOT.SUPP_AUG: every query is a group of %d consecutive "
+                         "rows)" % (len(q_sizes), aug, aug))
+    for g in range(len(q_sizes) // aug):
+        members = q_sizes[g * aug:(g + 1) * aug]
+        if any(m != members[0] for m in members):
+            raise ValueError("query group %d (rows %d .. %d) has members of different sizes %s: the rows of a FEW_SHOT.SUPP_AUG group "
+                             "must have one size (generalized_rcnn.py:236-250)" % (g, g * aug, (g + 1) * aug - 1, members))
+    return q_sizes[::aug]
+
+
 def box_cls_logits(box_cls_loss="ce_loss", soft_labeling=False):
     """Outputs of predictor.cls_score = logits at the head of a predictor row (roi_box_predictors.py:47-50,63-68,76-77): 2 for
     'ce_loss' and 'cxe_loss', 1 for the sigmoid losses ('focal_loss', 'mse_loss', 'l1_loss')."""

@@ -45,6 +45,14 @@ the padded shape of `queries`.  They ride the query backbone as B more rows of t
 first B rows only.  The box head scores the same sampled ROIs against them with the same weights and a margin loss is added
 (train_second_stage.py, include/oneshotdet_hip.h).  The state_dict has the keys and shapes of the plain 'ce_loss' model.
 `box_suppress_loss` [2] = (loss_cls_suppress, foreground rows) of the last step.  False (the default): every launch as it is.
+
+supp_aug / supp_aug_method (FEW_SHOT.SUPP_AUG with NUM_SUPP_AUG = supp_aug - 1, SUPP_AUG_METHOD 'avg' / 'max', generalized_rcnn.py:235-294):
+`queries` holds B*S*supp_aug rows, every query a group of supp_aug consecutive rows (a support crop and its augmentations, one size per
+group).  The query backbone runs on all rows and keeps their activations; one launch merges every group into one map per level
+(ops.supp_aug_reduce_levels) in front of the query pooling and the second stage, which run on B*S rows as they do without the option;
+the pooling backward and the second stage's query gradient accumulate into the merged maps' gradient, and one launch
+(ops.supp_aug_reduce_levels_bwd) expands it to B*S*supp_aug rows in front of the query backbone's backward.  Ordinary keywords like the
+shot count: not an option of a checkpoint.  1 (the default): nothing is launched.
 """
 import math
 import os
@@ -113,7 +121,8 @@ class TrainEngine(ForwardPass, BackwardPass, SecondStage, Update, State):
                  process_group=None, wgrad_side_stream=True, optimizer="fused", second_stage=False, ordered_wgrad=None,
                  exchange_single_rank=False, grad_wire_dtype=None, siamese_backbone=True, supp_roialign=True,
                  center_sample=True, loc_loss_type="giou", box_cls_loss="ce_loss", soft_labeling=False, soft_labeling_func="linear",
-                 linear_fusion=False, neg_support=False, lr_schedule=None):
+                 linear_fusion=False, neg_support=False, lr_schedule=None, supp_aug=1, supp_aug_method="avg"):
+        self.supp_aug, self.supp_aug_method = spec.supp_aug_mode(supp_aug, supp_aug_method, neg_support)
         # spec.MODEL_OPTIONS: ValueError by name before anything is built; every row becomes an attribute
         vars(self).update(spec.check_options("the TrainEngine", second_stage, **spec.options_in(locals()))._asdict())
         if not torch.cuda.is_available():
@@ -471,7 +480,7 @@ class TrainEngine(ForwardPass, BackwardPass, SecondStage, Update, State):
         return torch.cat([queries, neg_queries]), neg_sizes
 
     def forward_backward(self, images, queries, gt_boxes, gt_count, with_proposals=True, image_sizes=None, neg_queries=None):
-        """One training forward + backward.  images [B,3,H,W], queries [B*S,3,h,w] fp32 NCHW on the device;
+        """One training forward + backward.  images [B,3,H,W], queries [B*S,3,h,w] (supp_aug = A: [B*S*A,3,h,w]) fp32 NCHW on the device;
         gt_boxes [B, G, 4] fp32 xyxy, gt_count [B] int32.  Returns losses [4] = (cls, reg, centerness, num_pos).
         neg_queries (neg_support=True only, then required): the negative supports, of the type and padded shape of `queries`."""
         from . import model
@@ -489,6 +498,10 @@ class TrainEngine(ForwardPass, BackwardPass, SecondStage, Update, State):
             query_sizes = queries.image_sizes
         # neg_support: the query backbone's batch is (queries, negative supports); everything else reads `queries`
         qin, neg_sizes = self._neg_query_batch(images, queries, neg_queries)
+        # supp_aug: one size per group of `aug` rows (ValueError where a group's members differ, before anything is launched), as
+        # everything behind the merge sees it
+        aug, aug_method = self.supp_aug, self.supp_aug_method
+        q_sizes = spec.group_query_sizes([tuple(queries.shape[-2:])] * queries.shape[0] if query_sizes is None else query_sizes, aug)
         main, s1 = streams.current(), self.s1
         # train_step(defer_join) left the previous step's tail (last weight gradients, exchange, update, repack, proposals)
         # running on the side streams: the frozen prefix of this forward goes first, then the main stream joins them
@@ -508,8 +521,7 @@ class TrainEngine(ForwardPass, BackwardPass, SecondStage, Update, State):
         if deferred is None:
             join_previous()
         batch = images.shape[0]
-        shots = queries.shape[0] // batch
-        q_sizes = [tuple(queries.shape[-2:])] * queries.shape[0] if query_sizes is None else [tuple(v) for v in query_sizes]
+        shots = queries.shape[0] // (batch * aug)
         nq_sizes = None
         if self.neg_support:
             nq_sizes = [tuple(queries.shape[-2:])] * batch if neg_sizes is None else [tuple(v) for v in neg_sizes]
@@ -532,6 +544,7 @@ class TrainEngine(ForwardPass, BackwardPass, SecondStage, Update, State):
         if lock:
             (feats, qfeats), (tctx, qctx) = self.backbones_forward(images, qin, after_frozen=af)
             qfeats, nqfeats, qfeats_all = self._split_neg_rows(qfeats, batch)
+            qfeats = model.run_supp_aug(qfeats, aug, aug_method)         # qfeats_all keeps the un-merged maps
             pooled = pool(qfeats)
         else:       # the query backbone + pooling on the second stream beside the target backbone
             if deferred is not None and s1 is not None:
@@ -544,6 +557,7 @@ class TrainEngine(ForwardPass, BackwardPass, SecondStage, Update, State):
             with streams.on(side):
                 (qfeats,), (qctx,) = self._backbones_forward(self.BBS[1:], (qin,))
                 qfeats, nqfeats, qfeats_all = self._split_neg_rows(qfeats, batch)
+                qfeats = model.run_supp_aug(qfeats, aug, aug_method)     # qfeats_all keeps the un-merged maps
                 pooled = pool(qfeats)
             (feats,), (tctx,) = self._backbones_forward(self.BBS[:1], (images,), af)
             main.wait_stream(side)
@@ -619,6 +633,10 @@ class TrainEngine(ForwardPass, BackwardPass, SecondStage, Update, State):
                         ops.add_mask(ops.cast_f32(gq, self.dtype), None, None, out=full[lvl][batch:])
                 self._keep.append((dQ, qfeats_all))
                 dQ = full
+            if aug != 1:
+                # the merged maps' gradient (first + second stage) -> the query backbone's B*S*aug rows, one launch for all levels
+                self._keep.append((dQ, qfeats, qfeats_all))
+                dQ = ops.supp_aug_reduce_levels_bwd(qfeats_all, dQ, aug, aug_method)
             if not lock:
                 self.backbones_backward([qctx], [dQ], which0=1)
         dP = ops.correlate_levels(d_comb, pooled) if self.corr_levels else [ops.correlate(g, q) for g, q in zip(d_comb, pooled)]
