@@ -238,11 +238,93 @@ def pred_dgrad_pack_launch(w, cout, cin):
     return wd.view(cin, 1, 1, 64)
 
 
-def fcos_loss_grad_launch(head_out, gt_boxes, gt_count, scales, gamma, alpha):
-    """Phase 1 of osd_fcos_loss_levels: d loss / d (logit, centerness) and d loss / d (bbox_pred conv output) from the STORED
-    head outputs, by autograd of the loss restated in hotpath_ref.fcos_loss (fcos/loss.py:213-276).  reg = exp(scale * x), so
-    d/dx = d/dreg * reg * scale and d/dscale = sum d/dreg * reg * log(reg) / scale (fcos.py:95-97).
-    head_out: [(cls_ctr [N,H,W,4], reg [N,H,W,4])] per level.  -> per level (d_cls_ctr [N,H,W,2], d_x [N,H,W,4]), d_scale_raw"""
+def query_avgpool_launch(xs, batch):
+    """osd_query_avgpool_levels: nn.AdaptiveAvgPool2d((1, 1)) of every query map — the mean of the WHOLE map, padding included
+    (generalized_rcnn.py:87-94, 302-303) — in float64 per (row, channel), then the mean over the shots of a target image
+    (:100-104), per level: xs[l] NHWC [batch * shots, h, w, C] -> [batch, C] fp32."""
+    out = []
+    for x in xs:
+        r, c = x.shape[0], x.shape[-1]
+        per_row = x.double().mean(dim=(1, 2))
+        out.append(per_row.view(batch, r // batch, c).mean(dim=1).float())
+    return out
+
+
+def query_avgpool_bwd_launch(dqs, shapes, shots):
+    """osd_query_avgpool_levels_bwd: every pixel of map n gets dq[n // shots] / (h * w) / shots (the backward of the two means
+    above) -> [batch * shots, h, w, C] fp32 per level BEFORE the final rounding."""
+    out = []
+    for dq, (r, h, w, c) in zip(dqs, shapes):
+        v = (dq.double() / float(h * w) / float(shots)).float()
+        out.append(v.repeat_interleave(shots, dim=0)[:, None, None, :].expand(r, h, w, c).contiguous())
+    return out
+
+
+def supp_aug_reduce_launch(xs, aug, method):
+    """osd_supp_aug_reduce_levels, FEW_SHOT.SUPP_AUG (generalized_rcnn.py:280-288): group g = rows g*aug .. g*aug + aug - 1
+    (feat.split(aug, dim=0)) of xs[l] [G * aug, h, w, C] -> [G, h, w, C] fp32 BEFORE the final rounding.  'avg': the members
+    added in member order in fp32, then one division by aug (torch.mean of :285-286); 'max': the exact maximum (:287-288)."""
+    out = []
+    for x in xs:
+        g = x.float().reshape((x.shape[0] // aug, aug) + tuple(x.shape[1:]))
+        if method == "avg":
+            s = g[:, 0].clone()
+            for a in range(1, aug):
+                s = s + g[:, a]
+            out.append(s / float(aug))
+        elif method == "max":
+            out.append(g.max(dim=1)[0])
+        else:
+            raise ValueError("supp_aug method %r" % (method,))
+    return out
+
+
+def supp_aug_reduce_bwd_launch(xs, dys, aug, method):
+    """osd_supp_aug_reduce_levels_bwd: the gradient of the merge above w.r.t. xs, EVERY element written.  'avg': dy / aug to every
+    member; 'max': all of dy to the lowest-index member that attains the maximum of xs, 0 to the others — the rule of torch's CPU
+    max(dim) backward, which the reference's autograd applies to generalized_rcnn.py:287-288."""
+    out = []
+    for x, dy in zip(xs, dys):
+        g = x.float().reshape((x.shape[0] // aug, aug) + tuple(x.shape[1:]))
+        d = dy.float()
+        if method == "avg":
+            dx = (d / float(aug))[:, None].expand(g.shape)
+        elif method == "max":
+            m = g.max(dim=1, keepdim=True)[0]
+            first = torch.zeros(g.shape, dtype=torch.bool)
+            taken = torch.zeros(d.shape, dtype=torch.bool)
+            for a in range(aug):                                  # member order: the first one equal to the maximum takes it all
+                hit = (g[:, a] == m[:, 0]) & ~taken
+                first[:, a] = hit
+                taken |= hit
+            dx = torch.where(first, d[:, None].expand(g.shape), torch.zeros(()))
+        else:
+            raise ValueError("supp_aug method %r" % (method,))
+        out.append(dx.reshape(x.shape).contiguous())
+    return out
+
+
+def correlate_sweep_launch(x, q, classes):
+    """osd_correlate_levels_sweep (one level): row b * classes + k = x[b] * q[b * classes + k] — correlate_launch
+    (generalized_rcnn.py:307-311) on the map of image row // classes and query row `row`."""
+    rows = q.shape[0]
+    img = torch.arange(rows) // int(classes)
+    return correlate_launch(x.index_select(0, img), q)
+
+
+def correlate_gallery_launch(x, q, slots, classes):
+    """osd_correlate_levels_gallery (one level): row b * classes + k = x[b] * q[slots[b * classes + k]]."""
+    return correlate_sweep_launch(x, q.index_select(0, slots.long()), classes)
+
+
+def fcos_loss_grad_launch(head_out, gt_boxes, gt_count, scales, gamma, alpha, center_sample=True, loc_loss_type="giou"):
+    """Phase 1 of osd_fcos_loss_levels_opt: d loss / d (logit, centerness) and d loss / d (bbox_pred conv output) from the STORED
+    head outputs, by autograd of the loss restated in fcos_loss_modes.fcos_loss (fcos/loss.py:213-276; center_sample: FCOS.CENTER_SAMPLE,
+    :141-204; loc_loss_type: FCOS.LOC_LOSS_TYPE, layers/iou_loss.py:10-49; the default mode is hotpath_ref.fcos_loss to the last
+    bit).  reg = exp(scale * x), so d/dx = d/dreg * reg * scale and d/dscale = sum d/dreg * reg * log(reg) / scale (fcos.py:95-97).
+    head_out: [(cls_ctr [N,H,W,4], reg [N,H,W,4])] per level.  -> per level (d_cls_ctr [N,H,W,2], d_x [N,H,W,4]), d_scale_raw per
+    level (the sum before the division by scale), sum |terms| of that sum per level, (cls, reg, centerness loss, num_pos)"""
+    from . import fcos_loss_modes as flm
     logits, ctrs, regs = [], [], []
     for cc, rg in head_out:
         c = nchw(cc)
@@ -250,18 +332,21 @@ def fcos_loss_grad_launch(head_out, gt_boxes, gt_count, scales, gamma, alpha):
         ctrs.append(c[:, 1:2].clone().requires_grad_(True))
         regs.append(nchw(rg)[:, :4].clone().requires_grad_(True))
     gts = [gt_boxes[i, :int(gt_count[i])].float().numpy() for i in range(gt_boxes.shape[0])]
-    c, r, t, info = orc.fcos_loss(logits, regs, ctrs, gts, gamma=gamma, alpha=alpha, focal="cuda")
+    c, r, t, info = flm.fcos_loss(logits, regs, ctrs, gts, gamma=gamma, alpha=alpha, focal="cuda", center_sample=center_sample,
+                                  loc_loss_type=loc_loss_type)
     (c + r + t).backward()
-    outs, raws = [], []
+    outs, raws, raw_abs = [], [], []
     for lvl in range(len(head_out)):
         g_reg = regs[lvl].grad if regs[lvl].grad is not None else torch.zeros_like(regs[lvl])
         ds = g_reg * regs[lvl].detach()
         d_x = ds * float(scales[lvl])
-        raws.append(float((ds.double() * regs[lvl].detach().double().log()).sum()))
+        terms = ds.double() * regs[lvl].detach().double().log()
+        raws.append(float(terms.sum()))
+        raw_abs.append(float(terms.abs().sum()))
         gl = logits[lvl].grad if logits[lvl].grad is not None else torch.zeros_like(logits[lvl])
         gc = ctrs[lvl].grad if ctrs[lvl].grad is not None else torch.zeros_like(ctrs[lvl])
         outs.append((nhwc(torch.cat([gl, gc], 1)), nhwc(d_x)))
-    return outs, raws, (float(c), float(r), float(t), info["num_pos"])
+    return outs, raws, raw_abs, (float(c.detach()), float(r.detach()), float(t.detach()), info["num_pos"])
 
 
 # ---------------------------------------------------------------------------------------------------------------- comparison

@@ -242,7 +242,7 @@ def test_loss_gradient_launch_equals_autograd_through_the_exp_scale_head():
     (c + r + t).backward()
     head = [(torch.cat([lg, ct, torch.zeros_like(lg), torch.zeros_like(lg)], 1).detach().permute(0, 2, 3, 1),
              rg.detach().permute(0, 2, 3, 1)) for lg, ct, rg in zip(logits, ctrs, regs)]
-    outs, raws, _ = lr.fcos_loss_grad_launch(head, torch.from_numpy(gts[0])[None], torch.tensor([1]), scales, 2.0, 0.25)
+    outs, raws, _, _ = lr.fcos_loss_grad_launch(head, torch.from_numpy(gts[0])[None], torch.tensor([1]), scales, 2.0, 0.25)
     for lvl in range(2):
         torch.testing.assert_close(outs[lvl][0][..., 0:1].permute(0, 3, 1, 2), logits[lvl].grad, rtol=1e-4, atol=1e-7)
         torch.testing.assert_close(outs[lvl][0][..., 1:2].permute(0, 3, 1, 2), ctrs[lvl].grad, rtol=1e-4, atol=1e-7)
