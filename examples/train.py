@@ -86,8 +86,8 @@ def main():
                          "rule: sample i's negative support is the support crop of sample (i + 1) mod batch")
     ap.add_argument("--supp-aug", type=int, default=1, metavar="N",
                     help="query augmentation groups (FEW_SHOT.SUPP_AUG, NUM_SUPP_AUG = N - 1): every support is N consecutive rows merged "
-                         "behind the query backbone.  Here 1 (off) or 2 (the crop and its horizontal flip, the dataset's supp_aug=True); "
-                         "the dataset has no colour jitter for more")
+                         "behind the query backbone.  Here 1 (off), 2 (the crop and its horizontal flip, the dataset's supp_aug=True) or "
+                         "4 (NUM_SUPP_AUG 3: crop, flip and the colour-jittered crop and flip, the dataset's num_supp_aug=3)")
     ap.add_argument("--supp-aug-method", default="avg", choices=list(spec.SUPP_AUG_METHODS), help="FEW_SHOT.SUPP_AUG_METHOD")
     rec = solver.LRSchedule.of_record()
     ap.add_argument("--lr-steps", default=",".join(str(m) for m in rec.milestones), help="iterations at which the rate is multiplied by "
@@ -109,9 +109,10 @@ def main():
     # refused here, by name: l1_loss / cxe_loss without --soft-labeling, --neg-support in a combination it does not exist in
     spec.check_options("the example", not args.first_stage_only, **options)
     supp_aug, supp_aug_method = spec.supp_aug_mode(args.supp_aug, args.supp_aug_method, args.neg_support)
-    if supp_aug not in (1, 2):
-        raise SystemExit("--supp-aug %d: the dataset yields a support crop and its horizontal flip (supp_aug=True), which is --supp-aug 2; "
-                         "it has no colour-jitter supports for a larger group" % supp_aug)
+    if supp_aug not in (1, 2, 4):
+        raise SystemExit("--supp-aug %d: the dataset yields a support crop and its horizontal flip (supp_aug=True), which is --supp-aug 2, "
+                         "or both and their colour-jittered versions (num_supp_aug=3), which is --supp-aug 4; the reference has no "
+                         "NUM_SUPP_AUG for another group size" % supp_aug)
     rank, world = int(os.environ.get("RANK", "0")), int(os.environ.get("WORLD_SIZE", "1"))
     torch.cuda.set_device(int(os.environ.get("LOCAL_RANK", "0")))
     dtype = torch.bfloat16 if args.dtype == "bf16" else torch.float32
@@ -142,7 +143,7 @@ def main():
     tf_img, tf_supp = T.build_transforms(min_size=480, max_size=800, supp_min_size=128, supp_max_size=192, is_train=True)
     coco, pix = synthetic_coco(np.random.RandomState(1234))                # the same annotation set on every rank
     ds = dataset.FewShotCocoDataset(coco, lambda info: pix[info["id"]], is_train=True, shot=1, supp_area_threshold=40 * 40,
-                                    supp_aug=supp_aug == 2)
+                                    supp_aug=supp_aug == 2, num_supp_aug=3 if supp_aug == 4 else None)
     os.makedirs(args.out, exist_ok=True)
     for it in range(start, args.iters):
         imgs, supps, targets = [], [], []
@@ -153,9 +154,10 @@ def main():
             for t in tf_img.transforms[:2]:
                 dimg, tgt = t(dimg, tgt)
             imgs.append(dimg); targets.append(tgt)
-            # the support crop (coco.py:341); with --supp-aug 2 followed by its flip (coco.py:343-349): one group of consecutive rows
+            # the support crop (coco.py:341); with --supp-aug 2 followed by its flip (coco.py:343-349), with --supp-aug 4 also by the
+            # colour-jittered crop and flip (coco.py:447-452; DeviceImages already, made by one kernel call): one group of consecutive rows
             for crop in item["img_supp"][:supp_aug]:
-                supp = T.DeviceImage(crop)
+                supp = crop if isinstance(crop, T.DeviceImage) else T.DeviceImage(crop)
                 for t in tf_supp.transforms[:2]:
                     supp, _ = t(supp, None)
                 supps.append(supp)

@@ -177,6 +177,13 @@ SIGNATURES_SUPP_AUG = {
     "osd_supp_aug_reduce_levels_bwd": (_i, [_i, _p, _p, _p, _p, _i, _i, _i, _i, _i, _p]),
 }
 
+# include/oneshotdet_hip_color_jitter.h: the colour jitter of support crops (FEW_SHOT.NUM_SUPP_AUG = 3)
+COLOR_JITTER_MAX_IMAGES = 16      # OSD_COLOR_JITTER_MAX_IMAGES: images per launch pair
+SIGNATURES_COLOR_JITTER = {
+    "osd_color_jitter_workspace_bytes": (_i64, [_i, _p, _p]),
+    "osd_color_jitter_batch": (_i, [_i, _p, _p, _p, _p, _p, _p, _p]),
+}
+
 PRED_BWD_BOTH, PRED_BWD_DGRAD, PRED_BWD_WGRAD = 0, 1, 2       # `flags` of osd_conv2d_pred_bwd (OSD_PRED_BWD_*)
 
 _lib = None
@@ -198,7 +205,7 @@ def load():
     import torch  # noqa: F401  (loads libamdhip64 first)
     lib = C.CDLL(LIB_PATH)
     for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_BOX_MODES.items()) + list(SIGNATURES_SOFT_LABELS.items()) + \
-            list(SIGNATURES_SUPP_AUG.items()):
+            list(SIGNATURES_SUPP_AUG.items()) + list(SIGNATURES_COLOR_JITTER.items()):
         fn = getattr(lib, name)   # AttributeError if the symbol is missing
         fn.restype = res
         fn.argtypes = args

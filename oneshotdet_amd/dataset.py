@@ -14,7 +14,8 @@ What the reference does, restated (file:line = data/datasets/coco.py):
   * its supports (get_random_item_from_cat :292-355): the category's catalog, shuffled with the SAME random stream, walked
     until `shot` images other than the item's own are found whose largest object of the category has area >
     INPUT.SUPP_AREA_THRESHOLD; the crop is PIL's `crop((x, y, x + w, y + h))` of that object (coordinates rounded half to even,
-    black outside the image); with support augmentation each crop is followed by its horizontal flip (:343-349, NUM_SUPP_AUG 1).
+    black outside the image); with support augmentation each crop is followed by its horizontal flip (:343-349, NUM_SUPP_AUG 1);
+    with NUM_SUPP_AUG 3 the crop and the flip are followed by their colour-jittered versions (:286-294, :447-452).
 The random stream makes items order-dependent exactly as in the reference: the fixture (tests/golden/dataset.npz, recorded
 through the reference class) reads items 0 .. len - 1 once after construction, and so does the test.
 Images come from `load_image(image_info) -> uint8 HxWx3` (RGB); `transforms` / `supp_transforms` are applied to the query image
@@ -72,10 +73,33 @@ class FewShotCocoDataset(object):
     therefore equals the reference's only when no random transform runs between items — how tests/golden/dataset.npz was
     recorded (flip probability 0).  To reproduce the interleaving with is_train transforms, pass the SAME generator as `rng`
     here and to transforms.RandomHorizontalFlip(rng=...); `rng=random` (the module itself, after `random.seed(6666)`) is the
-    reference's arrangement exactly."""
+    reference's arrangement exactly.
+
+    Support augmentation.  `num_supp_aug=None` (the default) leaves the choice to `supp_aug`: False = the crop alone, True = the crop
+    and its horizontal flip (NUM_SUPP_AUG 1).  `num_supp_aug=3` (which implies augmentation) is the reference's other
+    configuration (:278-284): every support becomes FOUR rows, [crop, flip, jitter(crop), jitter(flip)], the order of :447-452 (the only
+    path of the reference that yields NUM_SUPP_AUG + 1 members).  The jitter is :286-294: per jittered member four factors,
+    `jitter_rng.uniform(0.1, 2)` four times in the order Color, Brightness, Contrast, Sharpness, the crop's four before the flip's four,
+    one support after the other.  `jitter_rng` defaults to a private `np.random.RandomState(seed)`; the reference draws from numpy's
+    GLOBAL stream, which is `jitter_rng=np.random` (the module itself).  `jitter(arrays, factors) -> images` is called once per item
+    with all jittered members ([2 * shot] arrays, factors [2 * shot, 4]); the default is transforms.color_jitter (the device kernel,
+    bit-exact PIL ImageEnhance), so the jittered members are DeviceImages, which the support transforms take like arrays.  Any other
+    `num_supp_aug` raises ValueError (the reference asserts 1 or 3, :279; 1 is `supp_aug=True` here).
+    One deliberate difference: :452 jitters `augmented_suppImgs[1]`, which with more than one shot is always the FIRST support's flip —
+    a row of another size than its group, which the model's equal-size assertion (modeling/detector/generalized_rcnn.py:241) refuses.
+    Here each support's own flip is jittered; with one shot the two are the same."""
 
     def __init__(self, coco, load_image, is_train=True, shot=1, exclude_contiguous=(), supp_area_threshold=80 * 80,
-                 supp_aug=False, transforms=None, supp_transforms=None, selected_category=-1, seed=6666, rng=None):
+                 supp_aug=False, transforms=None, supp_transforms=None, selected_category=-1, seed=6666, rng=None,
+                 num_supp_aug=None, jitter=None, jitter_rng=None):
+        if num_supp_aug is not None:
+            if isinstance(num_supp_aug, bool) or num_supp_aug != 3:
+                raise ValueError("num_supp_aug=%r: FEW_SHOT.NUM_SUPP_AUG is 1 (the crop and its flip: supp_aug=True, num_supp_aug=None) or "
+                                 "3 (both and their colour-jittered versions: num_supp_aug=3)" % (num_supp_aug,))
+            supp_aug = True
+        self.num_supp_aug = num_supp_aug
+        self.jitter = jitter
+        self.jitter_rng = jitter_rng if jitter_rng is not None else np.random.RandomState(seed)
         self.index = coco if isinstance(coco, CocoIndex) else CocoIndex(coco)
         self.load_image, self.is_train, self.shot = load_image, is_train, int(shot)
         self.supp_area_threshold, self.supp_aug = supp_area_threshold, bool(supp_aug)
@@ -111,7 +135,8 @@ class FewShotCocoDataset(object):
         return t
 
     def supports(self, category, exclude_image):
-        """`shot` support crops of `category` (uint8 arrays; each followed by its flip under support augmentation)"""
+        """`shot` support crops of `category` (uint8 arrays; each followed by its flip under support augmentation, and with
+        num_supp_aug=3 by the jittered crop and the jittered flip, which are whatever `jitter` returns)"""
         choices = list(self.catalog[category])
         self.rng.shuffle(choices)
         crops = []
@@ -133,6 +158,15 @@ class FewShotCocoDataset(object):
                              % (category, len(crops), self.shot))
         if self.supp_aug:
             crops = [v for c in crops for v in (c, np.ascontiguousarray(c[:, ::-1]))]
+        if self.num_supp_aug == 3:
+            factors = np.asarray([[self.jitter_rng.uniform(0.1, 2) for _ in range(4)] for _ in crops], dtype=np.float64)
+            jitter = self.jitter
+            if jitter is None:
+                from .transforms import color_jitter as jitter
+            jittered = list(jitter(crops, factors))
+            if len(jittered) != len(crops):
+                raise ValueError("jitter returned %d images for %d" % (len(jittered), len(crops)))
+            crops = [v for k in range(0, len(crops), 2) for v in (crops[k], crops[k + 1], jittered[k], jittered[k + 1])]
         return crops
 
     def __getitem__(self, idx):

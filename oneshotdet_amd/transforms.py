@@ -11,6 +11,10 @@ as the float CHW tensor the reference returns (Normalize) or directly into the p
 in the stem conv's NHWC4 input format.  Boxes follow with BoxList.resize / transpose semantics (bounding_box.py:91-166).
 
 There is no CPU path: a host uint8 array is uploaded, everything else happens on the device.
+
+The one step that changes pixel values ahead of the normalisation is the colour jitter of support crops (`color_jitter`,
+`DeviceImage.jittered`; data/datasets/coco.py:286-294, FEW_SHOT.NUM_SUPP_AUG = 3): uint8 in, uint8 out, bit-exact PIL ImageEnhance, one
+C call (csrc/color_jitter.hip) for a whole list of crops; its results travel through Resize / flip / collate like any other image.
 """
 import ctypes as C
 import math
@@ -68,6 +72,39 @@ class DeviceImage(object):
         if cx1 > cx0 and cy1 > cy0:
             out[cy0 - y0:cy1 - y0, cx0 - x0:cx1 - x0] = self.src[cy0:cy1, cx0:cx1]
         return DeviceImage(out)
+
+    def jittered(self, factors4):
+        """The reference's colour jitter (data/datasets/coco.py:286-294) with the four factors Color, Brightness, Contrast,
+        Sharpness: `color_jitter` on one image.  Like `crop`, only before any Resize / flip."""
+        return color_jitter([self], [factors4])[0]
+
+
+def color_jitter(images, factors):
+    """The reference's colour jitter of support crops (data/datasets/coco.py:286-294: PIL ImageEnhance Color, Brightness, Contrast,
+    Sharpness in a row, bit for bit) on a list of images in ONE call of osd_color_jitter_batch (csrc/color_jitter.hip).
+    images: uint8 [H, W, 3] arrays or tensors, or untransformed DeviceImages; factors: [n, 4], image i's four factors in that order
+    (float64 as drawn; each is converted to float32 once, as PIL does).  -> [DeviceImage], new images of the same sizes."""
+    images = [im if isinstance(im, DeviceImage) else DeviceImage(im) for im in images]
+    for im in images:
+        if im.flip or im.out_hw != (int(im.src.shape[0]), int(im.src.shape[1])):
+            raise ValueError("DeviceImage.jittered / color_jitter applies to the untransformed image")
+    n = len(images)
+    f = np.asarray(factors, dtype=np.float64)
+    if f.size != n * 4 or (n and f.shape[-1] != 4):
+        raise ValueError("color_jitter needs four factors (Color, Brightness, Contrast, Sharpness) per image: [%d, 4]" % n)
+    f = f.reshape(n, 4)
+    if n == 0:
+        return []
+    f32 = np.ascontiguousarray(f.astype(np.float32))
+    outs = [torch.empty_like(im.src) for im in images]
+    arr = lambda vals: (C.c_int32 * n)(*[int(v) for v in vals])      # noqa: E731
+    hs, ws = arr(im.src.shape[0] for im in images), arr(im.src.shape[1] for im in images)
+    need = int(_lib.load().osd_color_jitter_workspace_bytes(n, hs, ws))
+    wsp = torch.empty((need // 8 + 1,), device=images[0].src.device, dtype=torch.int64)
+    srcs = (C.c_void_p * n)(*[im.src.data_ptr() for im in images])
+    dsts = (C.c_void_p * n)(*[o.data_ptr() for o in outs])
+    _lib.call("osd_color_jitter_batch", n, srcs, hs, ws, f32.ctypes.data_as(C.c_void_p), dsts, ops._ptr(wsp), ops._stream())
+    return [DeviceImage(o) for o in outs]
 
 
 def _resize_boxes(target, new_size_wh):
