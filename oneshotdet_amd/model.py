@@ -7,6 +7,7 @@ Mirrors, function for function, the reference call stack of SURVEY.md §3.1:
     rpn = FCOSModule: FCOSHead + FCOSPostProcessor               (modeling/rpn/fcos/fcos.py, inference.py)
 All tensors between kernels are NHWC; state_dict names and OIHW shapes are the reference's (oneshotdet_amd/spec.py).
 """
+import collections
 import os
 
 import torch
@@ -29,6 +30,7 @@ def _bn(sd, p):
 RES_DOWN2X_OK = os.environ.get("OSD_NO_RES_DOWN2X", "0") == "0"      # A/B switch: copy the identity's even pixels instead (the form until round 6)
 FPN_OUT_GROUPED = os.environ.get("OSD_NO_FPN_GROUPED", "0") == "0"       # the FPN's P3 + P4 output convs as one launch
 FUSE_DOWNSAMPLE = os.environ.get("OSD_NO_FUSE_DS", "0") == "0"      # A/B switch: conv3 + downsample of a stage's first block as one GEMM
+C3DS = "conv3+downsample.0"      # that fused conv of a block (pack_conv3_downsample) in the by-name lookups of walk_backbones
 
 
 def pack_conv3_downsample(sd, p, dtype):
@@ -52,10 +54,11 @@ class BackboneWeights(object):
         b = prefix + "body."
         self.stem = ops.pack_conv(sd[b + "stem.conv1.weight"], bn=_bn(sd, b + "stem.bn1"), dtype=dtype, stem=True)
         self.blocks = []
+        self.convs = {"body.stem.conv1": self.stem}      # every packed conv by its name behind the prefix (walk_backbones)
         for si, nblocks in enumerate(spec.STAGE_BLOCKS):
             for bi in range(nblocks):
                 p = "%slayer%d.%d." % (b, si + 1, bi)
-                blk = {"stride": 2 if (bi == 0 and si > 0) else 1, "ds": None}
+                blk = {"ds": None}
                 if (p + "downsample.0.weight") in sd:
                     blk["ds"] = ops.pack_conv(sd[p + "downsample.0.weight"], bn=_bn(sd, p + "downsample.1"), dtype=dtype)
                     # bf16 only: the exact-fp32 engines stay on the reference's operation order (the fused sum rounds once
@@ -64,13 +67,15 @@ class BackboneWeights(object):
                 for i in (1, 2, 3):
                     blk["c%d" % i] = ops.pack_conv(sd["%sconv%d.weight" % (p, i)], bn=_bn(sd, "%sbn%d" % (p, i)),
                                                    dtype=dtype)
-                blk["last_of_stage"] = bi == nblocks - 1
                 self.blocks.append(blk)
+                for key, name in (("c1", "conv1"), ("c2", "conv2"), ("c3", "conv3"), ("ds", "downsample.0"), ("c3ds", C3DS)):
+                    if blk.get(key) is not None:
+                        self.convs[p[len(prefix):] + name] = blk[key]
         f = prefix + "fpn."
         self.fpn = {}
         for name in ("fpn_inner2", "fpn_inner3", "fpn_inner4", "fpn_layer2", "fpn_layer3", "fpn_layer4",
                      "top_blocks.p6", "top_blocks.p7"):
-            self.fpn[name] = ops.pack_conv(sd[f + name + ".weight"], bias=sd[f + name + ".bias"], dtype=dtype)
+            self.convs["fpn." + name] = self.fpn[name] = ops.pack_conv(sd[f + name + ".weight"], bias=sd[f + name + ".bias"], dtype=dtype)
 
 
 class HeadWeights(object):
@@ -96,107 +101,104 @@ class HeadWeights(object):
         self.scales_dev = torch.cat([sd["%sscales.%d.scale" % (prefix, i)].reshape(1) for i in range(5)]).float().contiguous()
 
 
-def run_backbone(wts, images, dtype, return_body=False):
-    """images NCHW fp32 -> [P3, P4, P5, P6, P7] NHWC.  resnet.py:138-145,295-315,332-337; fpn.py:43-75,95-99."""
-    x, (ho, wo) = ops.stem_input(images, dtype)
-    x = ops.conv2d(x, wts.stem, act=ACT_RELU, out_hw=(ho, wo))
-    x = ops.maxpool3x3s2(x)
-    feats = []
-    halved = False
-    for bi, blk in enumerate(wts.blocks):
-        s = blk["stride"]
-        if s == 2 and halved:
-            s, halved = 1, False
-        # C2 is read only by layer2.0's stride-2 1x1 convs (the FPN skips it): the last block of layer1 computes just the
-        # even pixels (3x3 at stride 2, then the 1x1 + residual on the quarter-size map); return_body keeps the full map
-        quarter = SKIP_UNUSED_C2 and not return_body and bi == spec.STAGE_BLOCKS[0] - 1
-        if blk.get("c3ds") is not None:       # first block of a stage: conv3 + downsample as one GEMM over [out | x]
-            out = ops.conv2d(x, blk["c1"], stride=s, act=ACT_RELU)
-            out = ops.conv2d(out, blk["c2"], pad=1, act=ACT_RELU)
-            x = ops.conv2d(out, blk["c3ds"], act=ACT_RELU, x2=x, x2_stride=s)
-            if blk["last_of_stage"]:
-                feats.append(x)
-            continue
-        identity = x if blk["ds"] is None else ops.conv2d(x, blk["ds"], stride=s)
-        out = ops.conv2d(x, blk["c1"], stride=s, act=ACT_RELU)
-        rmode = RES_SAME
-        if quarter:
-            out = ops.conv2d(out, blk["c2"], stride=2, pad=1, act=ACT_RELU)
-            if RES_DOWN2X_OK:        # the 1x1's epilogue reads the identity at (2 ho, 2 wo) itself (round 6: no strided copy of a 210 MB map)
-                rmode = RES_DOWN2X
+# How a caller wants the R-50-FPN graph walked ("One graph walk, three callers"): data, one instance per caller.
+#   fuse_stages       stages whose first block runs conv3 + downsample as one two-source GEMM, where that conv is packed (bf16)
+#   down2x_even_only  RES_DOWN2X for layer1's quarter-size last block only where every identity map has even H and W (else a strided copy)
+#   p7_relu_in        P7's input ReLU as the conv's prologue, one launch per branch (False: relu(P6) materialised, kept as maps["p6r"])
+#   skip_unused_c2, fpn_out_grouped    the OSD_FULL_C2 / OSD_NO_FPN_GROUPED switches as the caller reads them
+BackbonePolicy = collections.namedtuple("BackbonePolicy", "fuse_stages down2x_even_only p7_relu_in skip_unused_c2 fpn_out_grouped")
+
+
+def walk_backbones(conv, inputs, dtype, policy, save=None, after_frozen=None):
+    """THE R-50-FPN forward graph (resnet.py:138-145,295-315,332-337; fpn.py:43-75,95-99): stem, max-pool, 16 bottlenecks, top-down
+    FPN, P6, P7, for len(inputs) branches in lockstep: every layer is one ops.conv2d_multi launch over the branches (one branch: the
+    plain ops.conv2d launch, ops.conv2d_multi forwards it).  conv(j, name) -> the PackedConv of branch j's conv ("body.layer2.0.conv1",
+    "fpn.fpn_inner3", a block's C3DS: None where not packed).  save(si, bi, block) gets every bottleneck's per-branch lists (p, s, ds,
+    x, o1, o2, y); after_frozen() is called once the stems and layer1 (frozen: resnet.py:127-136) have been enqueued.
+    -> ([P3..P7] NHWC per branch, {c3, c4, c5, inner4, inner3, inner2, p5, p6, p6r: per-branch lists})."""
+    nb = range(len(inputs))
+
+    def pcs(name):
+        return [conv(j, name) for j in nb]
+    xs = []
+    for j in nb:
+        x, hw = ops.stem_input(inputs[j], dtype)
+        x = ops.conv2d(x, conv(j, "body.stem.conv1"), act=ACT_RELU, out_hw=hw)
+        xs.append(ops.maxpool3x3s2(x))
+    stage_out, halved = [], False
+    for si, nblocks in enumerate(spec.STAGE_BLOCKS):
+        for bi in range(nblocks):
+            p = "body.layer%d.%d." % (si + 1, bi)
+            s = 2 if (bi == 0 and si > 0) else 1
+            if s == 2 and halved:        # the stride already happened in the producer (below)
+                s, halved = 1, False
+            has_ds = bi == 0             # in_channels != out_channels -> downsample branch (resnet.py:243-251)
+            fused = pcs(p + C3DS) if has_ds and si in policy.fuse_stages else [None]
+            if fused[0] is not None:     # the 4x-wide downsample map is never written nor re-read as a residual
+                o1 = ops.conv2d_multi(xs, pcs(p + "conv1"), stride=s, act=ACT_RELU)
+                o2 = ops.conv2d_multi(o1, pcs(p + "conv2"), pad=1, act=ACT_RELU)
+                y = [ops.conv2d(o2[j], fused[j], act=ACT_RELU, x2=xs[j], x2_stride=s) for j in nb]
             else:
-                identity = identity[:, ::2, ::2].contiguous()
-            halved = True
-        else:
-            out = ops.conv2d(out, blk["c2"], pad=1, act=ACT_RELU)
-        x = ops.conv2d(out, blk["c3"], act=ACT_RELU, res=identity, res_mode=rmode)
-        if blk["last_of_stage"]:
-            feats.append(x)
-    c3, c4, c5 = feats[1], feats[2], feats[3]
-    f = wts.fpn
-    inner4 = ops.conv2d(c5, f["fpn_inner4"])
-    p5 = ops.conv2d(inner4, f["fpn_layer4"], pad=1)
-    inner3 = ops.conv2d(c4, f["fpn_inner3"], res=inner4, res_mode=RES_UP2X)
-    inner2 = ops.conv2d(c3, f["fpn_inner2"], res=inner3, res_mode=RES_UP2X)
-    if FPN_OUT_GROUPED:      # the P3 and P4 output convs as one launch: 400 + 100 pixel tiles = 1.95 rounds of 256 CUs instead of 1.56 and 0.4
-        p3, p4 = ops.conv2d_multi([inner2, inner3], [f["fpn_layer2"], f["fpn_layer3"]], pad=1)
+                identity = ops.conv2d_multi(xs, pcs(p + "downsample.0"), stride=s) if has_ds else xs
+                o1 = ops.conv2d_multi(xs, pcs(p + "conv1"), stride=s, act=ACT_RELU)
+                rmode = RES_SAME
+                # C2 (layer1's output) is read by nothing but layer2.0's two stride-2 1x1 convs (the FPN skips it, fpn.py:33,
+                # backbone.py:59): only its even pixels are ever used, so layer1's last block computes just those (its 3x3 at
+                # stride 2, its 1x1 + residual on the quarter-size map) and layer2.0 reads them at stride 1
+                if policy.skip_unused_c2 and si == 0 and bi == nblocks - 1:
+                    o2 = ops.conv2d_multi(o1, pcs(p + "conv2"), stride=2, pad=1, act=ACT_RELU)
+                    if RES_DOWN2X_OK and not (policy.down2x_even_only and any(t.shape[1] % 2 or t.shape[2] % 2 for t in identity)):
+                        rmode = RES_DOWN2X       # conv3's epilogue reads the identity at (2 ho, 2 wo): no strided copy of a 210 MB map
+                    else:
+                        identity = [t[:, ::2, ::2].contiguous() for t in identity]
+                    halved = True
+                else:
+                    o2 = ops.conv2d_multi(o1, pcs(p + "conv2"), pad=1, act=ACT_RELU)
+                y = ops.conv2d_multi(o2, pcs(p + "conv3"), act=ACT_RELU, residuals=identity, res_mode=rmode)
+            if save is not None:
+                save(si, bi, dict(p=p, s=s, ds=has_ds, x=xs, o1=o1, o2=o2, y=y))
+            xs = y
+        stage_out.append(xs)
+        if si == 0 and after_frozen is not None:
+            after_frozen()
+    m = dict(c3=stage_out[1], c4=stage_out[2], c5=stage_out[3])
+    m["inner4"] = ops.conv2d_multi(m["c5"], pcs("fpn.fpn_inner4"))
+    p5 = m["p5"] = ops.conv2d_multi(m["inner4"], pcs("fpn.fpn_layer4"), pad=1)
+    inner3 = m["inner3"] = ops.conv2d_multi(m["c4"], pcs("fpn.fpn_inner3"), residuals=m["inner4"], res_mode=RES_UP2X)
+    inner2 = m["inner2"] = ops.conv2d_multi(m["c3"], pcs("fpn.fpn_inner2"), residuals=inner3, res_mode=RES_UP2X)
+    if policy.fpn_out_grouped:
+        # the P3 and P4 output convs (fpn.py:66-75: same 3x3 256 -> 256 geometry, their own weights) as ONE launch: alone, P3's
+        # 400 pixel tiles are 1.56 rounds of the 256 CUs and P4's 100 fill 40 % of one; together 500 tiles are 1.95 rounds
+        # (the grouped-launch tuner may still cut it where that measures faster)
+        p34 = ops.conv2d_multi(inner2 + inner3, pcs("fpn.fpn_layer2") + pcs("fpn.fpn_layer3"), pad=1)
+        p3, p4 = p34[:len(nb)], p34[len(nb):]
     else:
-        p4 = ops.conv2d(inner3, f["fpn_layer3"], pad=1)
-        p3 = ops.conv2d(inner2, f["fpn_layer2"], pad=1)
-    p6 = ops.conv2d(p5, f["top_blocks.p6"], stride=2, pad=1)
-    p7 = ops.conv2d(p6, f["top_blocks.p7"], stride=2, pad=1, relu_in=True)
-    out = [p3, p4, p5, p6, p7]
-    return (out, feats) if return_body else out
+        p4 = ops.conv2d_multi(inner3, pcs("fpn.fpn_layer3"), pad=1)
+        p3 = ops.conv2d_multi(inner2, pcs("fpn.fpn_layer2"), pad=1)
+    p6 = m["p6"] = ops.conv2d_multi(p5, pcs("fpn.top_blocks.p6"), stride=2, pad=1)
+    if policy.p7_relu_in:            # relu prologue (conv2d only): tiny launches
+        m["p6r"] = None
+        p7 = [ops.conv2d(p6[j], conv(j, "fpn.top_blocks.p7"), stride=2, pad=1, relu_in=True) for j in nb]
+    else:                            # relu(P6), materialised: the P7 weight gradient reads it
+        m["p6r"] = [ops.add_mask(t, None, t) for t in p6]
+        p7 = ops.conv2d_multi(m["p6r"], pcs("fpn.top_blocks.p7"), stride=2, pad=1)
+    return [[p3[j], p4[j], p5[j], p6[j], p7[j]] for j in nb], m
+
+
+def run_backbone(wts, images, dtype):
+    """images NCHW fp32 -> [P3, P4, P5, P6, P7] NHWC: walk_backbones with one branch."""
+    policy = BackbonePolicy(fuse_stages=(0, 1, 2, 3), down2x_even_only=False, p7_relu_in=True, skip_unused_c2=SKIP_UNUSED_C2,
+                            fpn_out_grouped=FPN_OUT_GROUPED)
+    return walk_backbones(lambda j, name: wts.convs.get(name), (images,), dtype, policy)[0][0]
 
 
 def run_backbones(wt, wq, images, queries, dtype):
     """Target and query backbone (BackboneWeights wt / wq: generalized_rcnn.py:270-272, separately parameterised, same
     graph) in LOCKSTEP: every layer is one osd_conv2d_fwd_multi launch over (target, query), so the query branch's
     latency-sized launches ride in the tail of the target's.  -> ([P3..P7] target, [P3..P7] query), NHWC."""
-    xs = []
-    for wts, im in ((wt, images), (wq, queries)):
-        x, (ho, wo) = ops.stem_input(im, dtype)
-        x = ops.conv2d(x, wts.stem, act=ACT_RELU, out_hw=(ho, wo))
-        xs.append(ops.maxpool3x3s2(x))
-    feats = []
-    halved = False
-    for bi, (bt, bq) in enumerate(zip(wt.blocks, wq.blocks)):
-        s = bt["stride"]
-        if s == 2 and halved:
-            s, halved = 1, False
-        quarter = SKIP_UNUSED_C2 and bi == spec.STAGE_BLOCKS[0] - 1         # see run_backbone
-        identity = xs if bt["ds"] is None else ops.conv2d_multi(xs, [bt["ds"], bq["ds"]], stride=s)
-        out = ops.conv2d_multi(xs, [bt["c1"], bq["c1"]], stride=s, act=ACT_RELU)
-        rmode = RES_SAME
-        if quarter:
-            out = ops.conv2d_multi(out, [bt["c2"], bq["c2"]], stride=2, pad=1, act=ACT_RELU)
-            if RES_DOWN2X_OK and all(t.shape[1] % 2 == 0 and t.shape[2] % 2 == 0 for t in identity):
-                rmode = RES_DOWN2X
-            else:
-                identity = [t[:, ::2, ::2].contiguous() for t in identity]
-            halved = True
-        else:
-            out = ops.conv2d_multi(out, [bt["c2"], bq["c2"]], pad=1, act=ACT_RELU)
-        xs = ops.conv2d_multi(out, [bt["c3"], bq["c3"]], act=ACT_RELU, residuals=identity, res_mode=rmode)
-        if bt["last_of_stage"]:
-            feats.append(xs)
-    c3, c4, c5 = feats[1], feats[2], feats[3]
-
-    def f(name):
-        return [wt.fpn[name], wq.fpn[name]]
-    inner4 = ops.conv2d_multi(c5, f("fpn_inner4"))
-    p5 = ops.conv2d_multi(inner4, f("fpn_layer4"), pad=1)
-    inner3 = ops.conv2d_multi(c4, f("fpn_inner3"), residuals=inner4, res_mode=RES_UP2X)
-    inner2 = ops.conv2d_multi(c3, f("fpn_inner2"), residuals=inner3, res_mode=RES_UP2X)
-    if FPN_OUT_GROUPED:
-        p34 = ops.conv2d_multi(inner2 + inner3, f("fpn_layer2") + f("fpn_layer3"), pad=1)
-        p3, p4 = p34[:2], p34[2:]
-    else:
-        p4 = ops.conv2d_multi(inner3, f("fpn_layer3"), pad=1)
-        p3 = ops.conv2d_multi(inner2, f("fpn_layer2"), pad=1)
-    p6 = ops.conv2d_multi(p5, f("top_blocks.p6"), stride=2, pad=1)
-    p7 = [ops.conv2d(p6[j], f("top_blocks.p7")[j], stride=2, pad=1, relu_in=True) for j in (0, 1)]   # relu prologue: tiny
-    return [[p3[j], p4[j], p5[j], p6[j], p7[j]] for j in (0, 1)]
+    policy = BackbonePolicy(fuse_stages=(), down2x_even_only=True, p7_relu_in=True, skip_unused_c2=SKIP_UNUSED_C2,
+                            fpn_out_grouped=FPN_OUT_GROUPED)
+    return walk_backbones(lambda j, name: (wt, wq)[j].convs.get(name), (images, queries), dtype, policy)[0]
 
 
 _ROI_CACHE = {}

@@ -8,7 +8,7 @@ from . import streams
 
 from . import model as _model
 from . import ops, spec
-from .ops import ACT_EXP_SCALE, ACT_RELU, RES_DOWN2X, RES_SAME, RES_UP2X
+from .ops import ACT_EXP_SCALE
 
 SIZE_RANGES = ((-1.0, 64.0), (64.0, 128.0), (128.0, 256.0), (256.0, 512.0), (512.0, float(spec.INF)))
 
@@ -22,84 +22,23 @@ class ForwardPass(object):
         layer is ONE osd_conv2d_fwd_multi launch over (target, query), so the query branch's latency-sized launches (M = 8
         .. 8192 pixels) ride in the tail of the target's instead of costing ~110 launches of their own per step.
         after_frozen: called once the stems and layer1 (frozen: resnet.py:127-136) have been enqueued, before the first
-        layer that reads trainable weights.  Returns ([feats_target, feats_query], [ctx_target, ctx_query])."""
-        cv, dt = self.convs, self.dtype
-        nb = range(len(bbs))
+        layer that reads trainable weights.  Returns ([feats_target, feats_query], [ctx_target, ctx_query]).  The graph itself is
+        model.walk_backbones; this caller names the trainable convs, picks the training policy and keeps what backward reads."""
+        cv, nb = self.convs, range(len(bbs))
+        blocks = [[] for _ in nb]
 
-        def pcs(name):
-            return [cv[bb + name].pc for bb in bbs]
-        xs = []
-        for bb, im in zip(bbs, inputs):
-            x, (ho, wo) = ops.stem_input(im, dt)
-            x = ops.conv2d(x, cv[bb + "body.stem.conv1"].pc, act=ACT_RELU, out_hw=(ho, wo))
-            xs.append(ops.maxpool3x3s2(x))
-        blocks, stage_out = [[] for _ in nb], [[] for _ in nb]
-        halved = False
-        for si, nblocks in enumerate(spec.STAGE_BLOCKS):
-            for bi in range(nblocks):
-                p = "body.layer%d.%d." % (si + 1, bi)
-                s = 2 if (bi == 0 and si > 0) else 1
-                if s == 2 and halved:        # the stride already happened in the producer (see below)
-                    s, halved = 1, False
-                has_ds = (bbs[0] + p + "downsample.0") in cv
-                # C2 (layer1's output) is read by nothing but layer2.0's two stride-2 1x1 convs (the FPN skips it, fpn.py:33,
-                # backbone.py:59): only its even pixels are ever used, so the last block of the FROZEN layer1 computes
-                # just those — its 3x3 at stride 2, its 1x1 + residual on the quarter-size map — and layer2.0 reads
-                # them at stride 1.  Same values, 3/4 of two convs and of a 210 MB tensor gone.
-                quarter = self.skip_unused_c2 and si == 0 and bi == nblocks - 1 and len(spec.STAGE_BLOCKS) > 1
-                if si == 0 and has_ds and self._fused_l1:
-                    # frozen layer1.0 (no backward through it): conv3 + downsample as one GEMM over [conv2 output | block
-                    # input] (model.pack_conv3_downsample): the 4x-wide downsample map is never written nor re-read
-                    o1 = ops.conv2d_multi(xs, pcs(p + "conv1"), stride=s, act=ACT_RELU)
-                    o2 = ops.conv2d_multi(o1, pcs(p + "conv2"), pad=1, act=ACT_RELU)
-                    xs = [ops.conv2d(o2[j], self._fused_l1[bbs[j]], act=ACT_RELU, x2=xs[j], x2_stride=s) for j in nb]
-                    continue
-                identity = ops.conv2d_multi(xs, pcs(p + "downsample.0"), stride=s) if has_ds else xs
-                o1 = ops.conv2d_multi(xs, pcs(p + "conv1"), stride=s, act=ACT_RELU)
-                rmode = RES_SAME
-                if quarter:
-                    o2 = ops.conv2d_multi(o1, pcs(p + "conv2"), stride=2, pad=1, act=ACT_RELU)
-                    if _model.RES_DOWN2X_OK and all(t.shape[1] % 2 == 0 and t.shape[2] % 2 == 0 for t in identity):
-                        rmode = RES_DOWN2X       # conv3's epilogue reads the identity at (2 ho, 2 wo): no strided copy of the 210 MB map
-                    else:
-                        identity = [t[:, ::2, ::2].contiguous() for t in identity]
-                    halved = True
-                else:
-                    o2 = ops.conv2d_multi(o1, pcs(p + "conv2"), pad=1, act=ACT_RELU)
-                y = ops.conv2d_multi(o2, pcs(p + "conv3"), act=ACT_RELU, residuals=identity, res_mode=rmode)
-                if si >= 1:
-                    for j in nb:
-                        blocks[j].append(dict(p=p, s=s, ds=has_ds, x=xs[j], o1=o1[j], o2=o2[j], y=y[j],
-                                              first=(si == 1 and bi == 0)))
-                xs = y
-            for j in nb:
-                stage_out[j].append(xs[j])
-            if si == 0 and after_frozen is not None:
-                after_frozen()
-        c3, c4, c5 = ([so[i] for so in stage_out] for i in (1, 2, 3))
-        f = "fpn."
-        inner4 = ops.conv2d_multi(c5, pcs(f + "fpn_inner4"))
-        p5 = ops.conv2d_multi(inner4, pcs(f + "fpn_layer4"), pad=1)
-        inner3 = ops.conv2d_multi(c4, pcs(f + "fpn_inner3"), residuals=inner4, res_mode=RES_UP2X)
-        inner2 = ops.conv2d_multi(c3, pcs(f + "fpn_inner2"), residuals=inner3, res_mode=RES_UP2X)
-        if self.fpn_out_grouped:
-            # the P3 and P4 output convs (fpn.py:66-75: same 3x3 256 -> 256 geometry, their own weights) as ONE launch: alone, P3's
-            # 400 pixel tiles are 1.56 rounds of the 256 CUs and P4's 100 fill 40 % of one; together 500 tiles are 1.95 rounds —
-            # the tower launch's shape (the grouped-launch tuner may still cut it where that measures faster)
-            p34 = ops.conv2d_multi(inner2 + inner3, pcs(f + "fpn_layer2") + pcs(f + "fpn_layer3"), pad=1)
-            p3, p4 = p34[:len(inner2)], p34[len(inner2):]
-        else:
-            p4 = ops.conv2d_multi(inner3, pcs(f + "fpn_layer3"), pad=1)
-            p3 = ops.conv2d_multi(inner2, pcs(f + "fpn_layer2"), pad=1)
-        p6 = ops.conv2d_multi(p5, pcs(f + "top_blocks.p6"), stride=2, pad=1)
-        p6r = [ops.add_mask(t, None, t) for t in p6]        # relu(P6), materialised: the P7 weight gradient reads it
-        p7 = ops.conv2d_multi(p6r, pcs(f + "top_blocks.p7"), stride=2, pad=1)
-        feats, ctxs = [], []
-        for j in nb:
-            feats.append([p3[j], p4[j], p5[j], p6[j], p7[j]])
-            ctxs.append(dict(bb=bbs[j], blocks=blocks[j], c3=c3[j], c4=c4[j], c5=c5[j], inner4=inner4[j], inner3=inner3[j],
-                             inner2=inner2[j], p5=p5[j], p6=p6[j], p6r=p6r[j]))
-        return feats, ctxs
+        def conv(j, name):       # the only fused conv3 + downsample is the frozen layer1.0's (no backward through it), bf16 engines
+            return self._fused_l1.get(bbs[j]) if name.endswith(_model.C3DS) else cv[bbs[j] + name].pc
+
+        def save(si, bi, blk):   # the backward pass starts at layer2: layer1 is frozen
+            if si >= 1:
+                for j in nb:
+                    blocks[j].append(dict(p=blk["p"], s=blk["s"], ds=blk["ds"], x=blk["x"][j], o1=blk["o1"][j], o2=blk["o2"][j],
+                                          y=blk["y"][j], first=(si == 1 and bi == 0)))
+        policy = _model.BackbonePolicy(fuse_stages=(0,), down2x_even_only=True, p7_relu_in=False, skip_unused_c2=self.skip_unused_c2,
+                                       fpn_out_grouped=self.fpn_out_grouped)
+        feats, m = _model.walk_backbones(conv, inputs, self.dtype, policy, save, after_frozen)
+        return feats, [dict(bb=bbs[j], blocks=blocks[j], **{k: v[j] for k, v in m.items()}) for j in nb]
 
     def head_forward(self, feats):
         """FCOSHead.forward (fcos.py:83-99).  Layer by layer, BOTH towers over all five levels = ONE conv launch per layer
